@@ -11,6 +11,11 @@ One step = restore the matrix from a device-resident pristine copy (D2D,
 Protocol: W untimed warmup steps, then exactly K timed steps bracketed by a
 barrier + torch.cuda.synchronize on both sides; elapsed time is the MAX over
 ranks; rank 0 prints one JSON line.
+
+A plain run does only that. ``--full`` adds the driver-timed single-GPU extras
+(TRSM N=32768, SYEV N=20000, ZHEGV N=16384; ``config.extra_configs``).
+``--dump-outputs DIR`` writes the factor left by the last timed step as
+``DIR/<name>.npy`` (float64) so two builds can be compared output for output.
 """
 
 import argparse
@@ -119,6 +124,52 @@ def _extra_configs(device):
     return out
 
 
+_DUMP_FULL_MAX_BYTES = 32 << 20   # dump the whole factor up to this size
+_DUMP_SAMPLES = 2 << 20           # seeded lower-triangle samples beyond it
+_DUMP_TAIL_ROWS = 64              # trailing rows (depend on every panel)
+
+
+def _dump_outputs(out_dir, mat, rank):
+    """Write what the last timed step left in ``mat`` (the lower Cholesky
+    factor, as a caller of cholesky_factorization receives it) as float64
+    ``.npy`` files. Small factors are written whole (``L.npy``); large ones
+    as the diagonal, the last rows and a fixed seeded sample of the lower
+    triangle (~33 MB in all). Collective on a distributed grid."""
+    import numpy as np
+
+    d = mat.dist
+    n, nb = d.n, d.nb
+    distributed = mat.grid is not None and mat.grid.distributed
+    glob = mat.to_global() if distributed or n * n * 8 <= _DUMP_FULL_MAX_BYTES else None
+
+    def gather(rows, cols):
+        r = torch.as_tensor(rows, device=mat.storage.device)
+        c = torch.as_tensor(cols, device=mat.storage.device)
+        if glob is not None:
+            v = glob[r, c]
+        else:
+            v = mat.storage[r // nb, c // nb, r % nb, c % nb]
+        return v.to(torch.float64).cpu().numpy()
+
+    arrays = {}
+    if n * n * 8 <= _DUMP_FULL_MAX_BYTES:
+        arrays["L"] = torch.tril(glob).to(torch.float64).cpu().numpy()
+    else:
+        idx = np.arange(n, dtype=np.int64)
+        arrays["L_diag"] = gather(idx, idx)
+        tail = np.arange(n - _DUMP_TAIL_ROWS, n, dtype=np.int64)
+        rr, cc = np.meshgrid(tail, idx, indexing="ij")
+        arrays["L_tail_rows"] = np.where(cc <= rr, gather(rr, cc), 0.0)
+        rng = np.random.RandomState(20240607)
+        a = rng.randint(0, n, size=_DUMP_SAMPLES).astype(np.int64)
+        b = rng.randint(0, n, size=_DUMP_SAMPLES).astype(np.int64)
+        arrays["L_sample"] = gather(np.maximum(a, b), np.minimum(a, b))
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, arr in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -127,7 +178,13 @@ def main():
     p.add_argument("--n", type=int, default=32768)
     p.add_argument("--nb", type=int, default=512)
     p.add_argument("--device", type=str, default=None, help="debug override (cpu)")
+    p.add_argument("--full", action="store_true",
+                   help="also time the single-GPU extra configs (TRSM/SYEV/ZHEGV)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write the last timed step's factor as DIR/<name>.npy")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
 
     import torch.distributed as dist
 
@@ -194,12 +251,15 @@ def main():
     flops = n ** 3 / 3.0  # fp64 POTRF: n^3/6 mul + n^3/6 add
     gflops = flops / (elapsed / args.steps) / 1e9
 
-    # Extra BASELINE configs (3', 4, 5), measured in the same driver
-    # invocation on a single GPU so BENCH_rNN carries driver-timed values
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, mat, rank)
+
+    # Extra BASELINE configs (3', 4, 5), behind --full: measured in the same
+    # invocation on a single GPU so a full run carries driver-timed values
     # for more than the headline config. Each block has its own warmup and
     # barrier-bracketed timed region; results ride in config.extra_configs.
     extra = {}
-    if (world_size == 1 and device.type == "cuda" and n == 32768
+    if (args.full and world_size == 1 and device.type == "cuda" and n == 32768
             and os.environ.get("DLAF_BENCH_EXTRA", "1") != "0"):
         extra = _extra_configs(device)
 
