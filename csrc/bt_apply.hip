@@ -25,7 +25,7 @@
 
 #include <cstdint>
 
-#include "cplx.h"
+#include "kernels.h"
 
 namespace {
 
@@ -337,14 +337,14 @@ __global__ __launch_bounds__(512, 1) void bt_group_c128(
 
 }  // namespace
 
-extern "C" {
-
-int bt_apply_group_f64(double* E, int64_t nE, int64_t npad, const double* V,
-                       const double* VTt, int64_t base0, int b, int G, int R,
-                       int nwin, hipStream_t stream) {
-  if (G != 128 || b % 16 || b > 64 || R % 16 || R % b || nwin <= 0) return 0;
+template <>
+bool dlaf::bt_apply_group(double* E, int64_t nE, int64_t npad, const double* V,
+                          const double* VTt, int64_t base0, int b, int G,
+                          int R, int nwin, hipStream_t stream) {
+  if (G != 128 || b % 16 || b > 64 || R % 16 || R % b || nwin <= 0)
+    return false;
   const size_t sh64 = ((size_t)R + G) * 64 * sizeof(double);
-  if (sh64 > 160 * 1024) return 0;
+  if (sh64 > 160 * 1024) return false;
   // Tail split: Q = ceil(nE/64) column chunks; the last partial CU pass
   // would idle most of the chip, so the remainder columns run as a second
   // CW=32 launch (2 WGs/CU, half the per-WG work) — measured: 313 chunks
@@ -374,19 +374,26 @@ int bt_apply_group_f64(double* E, int64_t nE, int64_t npad, const double* V,
           <<<(int)((rest_cols + 31) / 32), 512, sh32, stream>>>(           \
               E + main_cols, rest_cols, nE, npad, V, VTt, base0, b, nwin); \
     }                                                                      \
-    return 1;                                                              \
+    return true;                                                           \
   }
   BT_CASE(192) BT_CASE(176) BT_CASE(160) BT_CASE(144)
 #undef BT_CASE
-  return 0;
+  return false;
 }
 
-int bt_apply_group_c128(double* E, int64_t nE, int64_t npad, const double* V,
-                        const double* VTt, int64_t base0, int b, int G, int R,
-                        int nwin, hipStream_t stream) {
-  if (G != 128 || b % 16 || b > 64 || R % 16 || R % b || nwin <= 0) return 0;
+// The complex kernel addresses E/V/VTt as interleaved (re, im) doubles.
+template <>
+bool dlaf::bt_apply_group(cplx<double>* Ec, int64_t nE, int64_t npad,
+                          const cplx<double>* Vc, const cplx<double>* VTtc,
+                          int64_t base0, int b, int G, int R, int nwin,
+                          hipStream_t stream) {
+  if (G != 128 || b % 16 || b > 64 || R % 16 || R % b || nwin <= 0)
+    return false;
+  double* E = interleaved(Ec);
+  const double* V = interleaved(Vc);
+  const double* VTt = interleaved(VTtc);
   const size_t sh = ((size_t)R + G) * 32 * 2 * sizeof(double);
-  if (sh > 160 * 1024) return 0;
+  if (sh > 160 * 1024) return false;
   const int blocks = (int)((nE + 31) / 32);
 #define BT_CASE(RT)                                                        \
   if (R == RT) {                                                           \
@@ -398,11 +405,9 @@ int bt_apply_group_c128(double* E, int64_t nE, int64_t npad, const double* V,
     bt_group_c128<128, RT><<<blocks, 512, sh, stream>>>(E, nE, npad, V,    \
                                                         VTt, base0, b,     \
                                                         nwin);             \
-    return 1;                                                              \
+    return true;                                                           \
   }
   BT_CASE(192) BT_CASE(176) BT_CASE(160) BT_CASE(144)
 #undef BT_CASE
-  return 0;
+  return false;
 }
-
-}  // extern "C"

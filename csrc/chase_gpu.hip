@@ -25,7 +25,7 @@
 
 #include <cstdint>
 
-#include "cplx.h"
+#include "kernels.h"
 
 namespace {
 
@@ -408,10 +408,12 @@ __global__ __launch_bounds__(256) void chase_gpu_k(
   }
 }
 
+}  // namespace
+
 template <typename T>
-void launch_chase(T* a, int64_t ld, int64_t size, int64_t b, T* vstore,
-                  const int64_t* offsets, int32_t* done, int32_t* abortf,
-                  hipStream_t stream) {
+void dlaf::chase_gpu(T* a, int64_t ld, int64_t size, int64_t b, T* vstore,
+                     const int64_t* offsets, int32_t* done, int32_t* abortf,
+                     hipStream_t stream) {
   int64_t nsweeps = size - 2;
   if (nsweeps <= 0) return;
   const size_t shbytes = (size_t)b * (2 * b + 2) * sizeof(T);
@@ -439,33 +441,11 @@ void launch_chase(T* a, int64_t ld, int64_t size, int64_t b, T* vstore,
       a, ld, size, b, vstore, offsets, done, abortf, nsweeps);
 }
 
-}  // namespace
-
-extern "C" {
-
-void chase_gpu_f64(double* a, int64_t ld, int64_t size, int64_t b,
-                   double* vstore, const int64_t* offsets, int32_t* done,
-                   int32_t* abortf, hipStream_t stream) {
-  launch_chase(a, ld, size, b, vstore, offsets, done, abortf, stream);
-}
-void chase_gpu_f32(float* a, int64_t ld, int64_t size, int64_t b, float* vstore,
-                   const int64_t* offsets, int32_t* done, int32_t* abortf,
-                   hipStream_t stream) {
-  launch_chase(a, ld, size, b, vstore, offsets, done, abortf, stream);
-}
-void chase_gpu_c128(double* a, int64_t ld, int64_t size, int64_t b,
-                    double* vstore, const int64_t* offsets, int32_t* done,
-                    int32_t* abortf, hipStream_t stream) {
-  launch_chase(reinterpret_cast<cplx<double>*>(a), ld, size, b,
-               reinterpret_cast<cplx<double>*>(vstore), offsets, done, abortf,
-               stream);
-}
-void chase_gpu_c64(float* a, int64_t ld, int64_t size, int64_t b, float* vstore,
-                   const int64_t* offsets, int32_t* done, int32_t* abortf,
-                   hipStream_t stream) {
-  launch_chase(reinterpret_cast<cplx<float>*>(a), ld, size, b,
-               reinterpret_cast<cplx<float>*>(vstore), offsets, done, abortf,
-               stream);
-}
-
-}  // extern "C"
+#define INSTANTIATE(S)                                                     \
+  template void dlaf::chase_gpu(S*, int64_t, int64_t, int64_t, S*,         \
+                                const int64_t*, int32_t*, int32_t*, hipStream_t);
+INSTANTIATE(double)
+INSTANTIATE(float)
+INSTANTIATE(cplx<double>)
+INSTANTIATE(cplx<float>)
+#undef INSTANTIATE

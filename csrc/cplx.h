@@ -50,3 +50,14 @@ struct ScalarTraits<cplx<T>> {
   static __device__ inline cplx<T> from_real(T v) { return {v, T(0)}; }
   static __device__ inline cplx<T> zero() { return {T(0), T(0)}; }
 };
+
+// Kernels that address complex operands as interleaved (re, im) reals take
+// their pointers through here; cplx<T> is exactly that pair.
+template <typename T>
+inline const T* interleaved(const cplx<T>* p) {
+  return reinterpret_cast<const T*>(p);
+}
+template <typename T>
+inline T* interleaved(cplx<T>* p) {
+  return reinterpret_cast<T*>(p);
+}

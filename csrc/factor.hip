@@ -1,94 +1,17 @@
 // Single-tile factorization building blocks for CDNA4.
 //
-// * potrf_block: single-workgroup LDS-resident Cholesky of a leading n x n
-//   block (n <= 128 real / n <= 64 complex, limited by 160 KiB LDS). The tile
-//   Cholesky of an nb x nb tile is orchestrated on the host (ext.cpp) as
-//   potrf_block + column-parallel block inverse + fused GEMM panel/trailing
-//   updates — the per-tile analog of the right-looking algorithm, replacing the
-//   reference's rocSOLVER potrf call.
+// * potrf_invert_block: single-workgroup LDS-resident Cholesky of one diagonal
+//   block fused with its inversion. The tile Cholesky of an nb x nb tile is
+//   orchestrated on the host (ext.cpp) as potrf_invert_block + fused GEMM
+//   panel/trailing updates against the block inverse — the per-tile analog of
+//   the right-looking algorithm, replacing the reference's rocSOLVER potrf
+//   call.
 // * trtri_lower: column-parallel lower-triangular inverse (thread-per-column
 //   forward substitution). Triangular solves everywhere in the library are
 //   GEMMs against these block inverses — the standard GPU TRSM trade.
 #include "kernels.h"
-#include "cplx.h"
 
 namespace {
-
-template <typename S, int BSZ>
-__launch_bounds__(256) __global__ void potrf_block_k(S* A, int n, int ld) {
-  using TR = ScalarTraits<S>;
-  using RT = typename TR::real_t;
-  __shared__ S L[BSZ][BSZ + 1];
-  const int tid = threadIdx.x;
-
-  // load (full block; only the lower triangle is referenced)
-  for (int e = tid; e < BSZ * BSZ; e += 256) {
-    const int i = e / BSZ, j = e % BSZ;
-    L[i][j] = (i < n && j < n) ? A[(int64_t)i * ld + j] : TR::zero();
-  }
-  __syncthreads();
-
-  const int ncb = (n + 15) / 16;
-  for (int cb = 0; cb < ncb; ++cb) {
-    const int c0 = cb * 16;
-    const int bsz = min(16, n - c0);
-    // 1) factor the 16x16 diagonal block with DEFERRED column scaling
-    //    (LDL^T-style elimination on unscaled columns, one barrier per step:
-    //     U[i][j] -= U[i][p] conj(U[j][p]) / U[p][p], then L[:,j] = U[:,j] /
-    //     sqrt(U[j][j]) in one scale pass).
-    {
-      const int i = tid / 16, j = tid % 16;
-      for (int p = 0; p < bsz; ++p) {
-        const RT s = RT(1) / TR::real(L[c0 + p][c0 + p]);
-        if (i < bsz && j < bsz && j > p && j <= i)
-          L[c0 + i][c0 + j] -= (L[c0 + i][c0 + p] * TR::conj(L[c0 + j][c0 + p])) * s;
-        __syncthreads();
-      }
-      // snapshot the column scale BEFORE any thread rewrites the diagonal
-      const bool act = (i < bsz && j < bsz && j <= i);
-      const RT sc = act ? RT(1) / sqrt(TR::real(L[c0 + j][c0 + j])) : RT(1);
-      __syncthreads();
-      if (act) L[c0 + i][c0 + j] = L[c0 + i][c0 + j] * sc;
-      __syncthreads();
-    }
-    // 2) panel solve: rows below vs the diagonal block (X * D^H = A)
-    {
-      const int r = c0 + 16 + tid;
-      if (r < n) {
-        for (int j = 0; j < bsz; ++j) {
-          S x = L[r][c0 + j];
-          for (int p = 0; p < j; ++p) x -= L[r][c0 + p] * TR::conj(L[c0 + j][c0 + p]);
-          L[r][c0 + j] = x * (RT(1) / TR::real(L[c0 + j][c0 + j]));
-        }
-      }
-      __syncthreads();
-    }
-    // 3) trailing update (lower part only)
-    {
-      const int t0 = c0 + 16;
-      const int nt = n - t0;
-      if (nt > 0) {
-        for (int e = tid; e < nt * nt; e += 256) {
-          const int i = e / nt, j = e % nt;
-          if (j <= i) {
-            S s = L[t0 + i][c0];
-            S acc = s * TR::conj(L[t0 + j][c0]);
-            for (int p = 1; p < bsz; ++p)
-              acc += L[t0 + i][c0 + p] * TR::conj(L[t0 + j][c0 + p]);
-            L[t0 + i][t0 + j] -= acc;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-
-  // store lower triangle (incl. diagonal)
-  for (int e = tid; e < BSZ * BSZ; e += 256) {
-    const int i = e / BSZ, j = e % BSZ;
-    if (i < n && j < n && j <= i) A[(int64_t)i * ld + j] = L[i][j];
-  }
-}
 
 // Single-workgroup LDS-resident variant for blocks (n <= 128 real / 64
 // complex): staging through LDS removes the global-latency-bound serial chain
@@ -159,13 +82,17 @@ __launch_bounds__(256) __global__ void potrf_invert_block_k(S* A, int n,
     for (int cb = 0; cb < ncb; ++cb) {
       const int c0 = cb * 16;
       const int bsz16 = min(16, n - c0);
-      // deferred-scaling 16x16 diagonal factor (see potrf_block_k)
+      // factor the 16x16 diagonal block with DEFERRED column scaling
+      // (LDL^T-style elimination on unscaled columns, one barrier per step:
+      //  U[i][j] -= U[i][p] conj(U[j][p]) / U[p][p], then L[:,j] = U[:,j] /
+      //  sqrt(U[j][j]) in one scale pass).
       for (int p = 0; p < bsz16; ++p) {
         const RT s = RT(1) / TR::real(L[c0 + p][c0 + p]);
         if (ti < bsz16 && tj < bsz16 && tj > p && tj <= ti)
           L[c0 + ti][c0 + tj] -= (L[c0 + ti][c0 + p] * TR::conj(L[c0 + tj][c0 + p])) * s;
         __syncthreads();
       }
+      // snapshot the column scale BEFORE any thread rewrites the diagonal
       const bool act = (ti < bsz16 && tj < bsz16 && tj <= ti);
       const RT sc = act ? RT(1) / sqrt(TR::real(L[c0 + tj][c0 + tj])) : RT(1);
       __syncthreads();
@@ -353,91 +280,32 @@ __global__ void trtri_lower_k(const S* L, S* T, int n, int ldl, int ldt,
 
 }  // namespace
 
-extern "C" {
-
-// Fused factor (optional) + block inverse. Tout is the BSZ x BSZ dinv block.
-// BSZ = 64 for ALL dtypes: the 64-block kernel needs ~73 KiB LDS, so it can
-// co-reside with trailing-update GEMM blocks on a CU — a 128-block (160 KiB)
-// kernel can never be scheduled next to them and serializes the lookahead.
-void potrf_invert_block_f64(double* A, int n, int ld, double* Tout,
-                            int do_factor, hipStream_t stream) {
-  potrf_invert_block_k<double, 64>
+// Tout is the kPotrfBsz x kPotrfBsz dinv block (see kernels.h for the size).
+template <typename S>
+void dlaf::potrf_invert_block(S* A, int n, int ld, S* Tout, int do_factor,
+                              hipStream_t stream) {
+  potrf_invert_block_k<S, kPotrfBsz>
       <<<1, 256, 0, stream>>>(A, n, ld, Tout, do_factor);
 }
-void potrf_invert_block_f32(float* A, int n, int ld, float* Tout,
-                            int do_factor, hipStream_t stream) {
-  potrf_invert_block_k<float, 64>
-      <<<1, 256, 0, stream>>>(A, n, ld, Tout, do_factor);
-}
-void potrf_invert_block_c128(double* A, int n, int ld, double* Tout,
-                             int do_factor, hipStream_t stream) {
-  potrf_invert_block_k<cplx<double>, 64><<<1, 256, 0, stream>>>(
-      reinterpret_cast<cplx<double>*>(A), n, ld,
-      reinterpret_cast<cplx<double>*>(Tout), do_factor);
-}
-void potrf_invert_block_c64(float* A, int n, int ld, float* Tout,
-                            int do_factor, hipStream_t stream) {
-  potrf_invert_block_k<cplx<float>, 64><<<1, 256, 0, stream>>>(
-      reinterpret_cast<cplx<float>*>(A), n, ld,
-      reinterpret_cast<cplx<float>*>(Tout), do_factor);
-}
 
-void potrf_block128_f64(double* A, int n, int ld, hipStream_t stream) {
-  potrf_block_k<double, 128><<<1, 256, 0, stream>>>(A, n, ld);
-}
-void potrf_block128_f32(float* A, int n, int ld, hipStream_t stream) {
-  potrf_block_k<float, 128><<<1, 256, 0, stream>>>(A, n, ld);
-}
-// complex: block size 64 (LDS limit); `A` is the interleaved base, ld in
-// complex elements.
-void potrf_block128_c128(double* A, int n, int ld, hipStream_t stream) {
-  potrf_block_k<cplx<double>, 64>
-      <<<1, 256, 0, stream>>>(reinterpret_cast<cplx<double>*>(A), n, ld);
-}
-void potrf_block128_c64(float* A, int n, int ld, hipStream_t stream) {
-  potrf_block_k<cplx<float>, 64>
-      <<<1, 256, 0, stream>>>(reinterpret_cast<cplx<float>*>(A), n, ld);
-}
-
-void trtri_lower_f64(const double* L, double* T, int n, int ldl, int ldt,
-                     int unit_diag, hipStream_t stream) {
-  if (n <= 128)
-    trtri_block_lds_k<double, 128>
+template <typename S>
+void dlaf::trtri_lower(const S* L, S* T, int n, int ldl, int ldt,
+                       int unit_diag, hipStream_t stream) {
+  // largest block whose [BSZ][BSZ+1] LDS image fits: 64 for c128, else 128
+  constexpr int BSZ = sizeof(S) == 16 ? 64 : 128;
+  if (n <= BSZ)
+    trtri_block_lds_k<S, BSZ>
         <<<1, 256, 0, stream>>>(L, T, n, ldl, ldt, unit_diag);
   else
-    trtri_lower_k<double>
+    trtri_lower_k<S>
         <<<(n + 255) / 256, 256, 0, stream>>>(L, T, n, ldl, ldt, unit_diag);
-}
-void trtri_lower_f32(const float* L, float* T, int n, int ldl, int ldt,
-                     int unit_diag, hipStream_t stream) {
-  if (n <= 128)
-    trtri_block_lds_k<float, 128>
-        <<<1, 256, 0, stream>>>(L, T, n, ldl, ldt, unit_diag);
-  else
-    trtri_lower_k<float>
-        <<<(n + 255) / 256, 256, 0, stream>>>(L, T, n, ldl, ldt, unit_diag);
-}
-void trtri_lower_c128(const double* L, double* T, int n, int ldl, int ldt,
-                      int unit_diag, hipStream_t stream) {
-  auto Lc = reinterpret_cast<const cplx<double>*>(L);
-  auto Tc = reinterpret_cast<cplx<double>*>(T);
-  if (n <= 64)
-    trtri_block_lds_k<cplx<double>, 64>
-        <<<1, 256, 0, stream>>>(Lc, Tc, n, ldl, ldt, unit_diag);
-  else
-    trtri_lower_k<cplx<double>>
-        <<<(n + 255) / 256, 256, 0, stream>>>(Lc, Tc, n, ldl, ldt, unit_diag);
-}
-void trtri_lower_c64(const float* L, float* T, int n, int ldl, int ldt,
-                     int unit_diag, hipStream_t stream) {
-  auto Lc = reinterpret_cast<const cplx<float>*>(L);
-  auto Tc = reinterpret_cast<cplx<float>*>(T);
-  if (n <= 128)
-    trtri_block_lds_k<cplx<float>, 128>
-        <<<1, 256, 0, stream>>>(Lc, Tc, n, ldl, ldt, unit_diag);
-  else
-    trtri_lower_k<cplx<float>>
-        <<<(n + 255) / 256, 256, 0, stream>>>(Lc, Tc, n, ldl, ldt, unit_diag);
 }
 
-}  // extern "C"
+#define INSTANTIATE(S)                                                       \
+  template void dlaf::potrf_invert_block(S*, int, int, S*, int, hipStream_t); \
+  template void dlaf::trtri_lower(const S*, S*, int, int, int, int, hipStream_t);
+INSTANTIATE(double)
+INSTANTIATE(float)
+INSTANTIATE(cplx<double>)
+INSTANTIATE(cplx<float>)
+#undef INSTANTIATE

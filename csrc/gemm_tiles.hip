@@ -1,12 +1,19 @@
-// Fused batched tile GEMM for CDNA4 (gfx950) on fp64/fp32 MFMA.
+// Fused batched tile GEMM for CDNA4 (gfx950) on fp64/fp32 MFMA: the entry
+// points (dlaf::gemm_tiles) and the guarded register-staged kernels.
 //
 // One kernel launch processes a LIST of tile-triples (GemmDesc): this is how a
 // whole trailing update (SYRK/HERK sweep), panel solve, or back-transform step
-// becomes a single launch with enough workgroups to fill 256 CUs. Each
-// workgroup computes one BMxBN block of one C tile:
-//   real    (f64/f32): BM=BN=128, BK=16, 4 waves, 64x64 per wave, 4x4 frags of
-//                      mfma_{f64,f32}_16x16x4 (exact fp64/fp32, the CDNA4
-//                      "SGEMM-class" MFMA at the vector-f64/f32 rate).
+// becomes a single launch with enough workgroups to fill 256 CUs.
+//
+// Layout of the GEMM layer:
+//   gemm_common.h      Mfma<T>, v4d/v4f, xcd_remap
+//   gemm_tiles_v2.hip  glds kernels: full tiles, C not aliasing A (hot phases)
+//   gemm_tiles.hip     this file: gemm_tiles() tries v2, else launches the
+//                      kernels below, which take edge shapes (M, N, K not
+//                      multiples of the block) and in-place panel applies.
+// Each workgroup here computes one BMxBN block of one C tile:
+//   real    (f64/f32): BM=128, BN=64|128, BK=16, 4 waves, 4 x BN/32 frags of
+//                      mfma_{f64,f32}_16x16x4.
 //   complex (c128/c64): BM=BN=64, BK=16, 4 waves, 32x32 per wave, 2x2 frags,
 //                      4 MFMA per fragment pair (re/im cross terms).
 //
@@ -18,34 +25,9 @@
 // inner loop is layout-independent. Out-of-range rows/cols (edge blocks when
 // M,N,K are not multiples of the block sizes) stage zeros and stores are
 // guarded, so arbitrary sizes are supported.
-#include "kernels.h"
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
+#include "gemm_common.h"
 
 namespace {
-
-template <typename T>
-struct Mfma;
-template <>
-struct Mfma<double> {
-  using acc_t = v4d;
-  static __device__ inline acc_t mma(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  // D row of (lane, reg): measured on gfx950 (tools/probe_mfma_f64.hip):
-  // row = (lane>>4) + 4*reg  (stride-4 between regs, UNLIKE the f32 form)
-  static __device__ inline int acc_row(int lk, int r) { return lk + 4 * r; }
-};
-template <>
-struct Mfma<float> {
-  using acc_t = v4f;
-  static __device__ inline acc_t mma(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  // f32 16x16x4: row = 4*(lane>>4) + reg (cdna_hip_programming.md §3)
-  static __device__ inline int acc_row(int lk, int r) { return lk * 4 + r; }
-};
 
 // ---------------- real kernel ----------------
 
@@ -55,33 +37,22 @@ struct Mfma<float> {
 //   BN = 128 ("in-place-safe"): wave tile 64x64 -> a single column block spans
 //        the whole N of a panel-apply, making X = X * dinv^H safe in place
 //        (every workgroup reads all of its A rows before writing them).
-template <typename T, int OPA, int OPB, int BN, int BK = 16, bool DBUF = false,
-          bool GUARD = true>
+template <typename T, int OPA, int OPB, int BN, bool GUARD>
 __launch_bounds__(256) __global__ void gemm_tiles_k(
     const GemmDesc* __restrict__ descs, const T* __restrict__ A,
     const T* __restrict__ B, T* __restrict__ C, int M, int N, int K, int lda,
     int ldb, int ldc, T alpha, T beta, int mblocks, int nblocks) {
-  constexpr int BM = 128;
+  constexpr int BM = 128, BK = 16;
   constexpr int LA = BM * BK / 256;  // elements staged per thread (A)
   constexpr int LB = BK * BN / 256;
   constexpr int WCW = BN / 2;        // wave tile columns
   constexpr int NFRAG = WCW / 16;
   using acc_t = typename Mfma<T>::acc_t;
 
-  __shared__ T As[DBUF ? 2 : 1][BM][BK + 1];
-  __shared__ T Bs[DBUF ? 2 : 1][BK][BN + 2];
+  __shared__ T As[1][BM][BK + 1];
+  __shared__ T Bs[1][BK][BN + 2];
 
-  int wg = blockIdx.x;
-  if constexpr (DBUF) {
-    // (variant 2 doubles as the XCD-swizzle experiment) remap so each XCD's
-    // round-robin share becomes a CONTIGUOUS block-index range: blocks of one
-    // desc then co-reside in one XCD's L2 and share A/B tile lines.
-    const int nx = 8;
-    const int g = gridDim.x;
-    const int per = g / nx, rem8 = g % nx;
-    const int xcd = wg % nx, pos = wg / nx;
-    wg = xcd * per + (xcd < rem8 ? xcd : rem8) + pos;
-  }
+  const int wg = blockIdx.x;
   const int per_desc = mblocks * nblocks;
   const GemmDesc d = descs[wg / per_desc];
   const int rem = wg % per_desc;
@@ -214,25 +185,12 @@ __launch_bounds__(256) __global__ void gemm_tiles_k(
 
   load_step(0, ra, rb);
 
-  if constexpr (DBUF) {
-    // one barrier per K-step: compute buf s&1 while staging s+1 into 1-(s&1)
+  for (int s = 0; s < total_steps; ++s) {
     stage(0, ra, rb);
     __syncthreads();
-    for (int s = 0; s < total_steps; ++s) {
-      const int cur = s & 1;
-      if (s + 1 < total_steps) load_step(s + 1, ra, rb);
-      compute(cur);
-      if (s + 1 < total_steps) stage(1 - cur, ra, rb);
-      __syncthreads();
-    }
-  } else {
-    for (int s = 0; s < total_steps; ++s) {
-      stage(0, ra, rb);
-      __syncthreads();
-      if (s + 1 < total_steps) load_step(s + 1, ra, rb);  // overlaps MFMA below
-      compute(0);
-      __syncthreads();  // LDS reuse barrier
-    }
+    if (s + 1 < total_steps) load_step(s + 1, ra, rb);  // overlaps MFMA below
+    compute(0);
+    __syncthreads();  // LDS reuse barrier
   }
 
   // epilogue: C = alpha*acc + beta*C
@@ -443,180 +401,82 @@ __launch_bounds__(256) __global__ void gemm_tiles_cplx_k(
     }
 }
 
-template <typename T>
-int v2_dispatch(const GemmDesc* descs, int ndesc, const T* A, const T* B, T* C,
-                int M, int N, int K, int lda, int ldb, int ldc, int opA,
-                int opB, T alpha, T beta, hipStream_t stream);
-template <>
-int v2_dispatch<double>(const GemmDesc* d, int n, const double* A,
-                        const double* B, double* C, int M, int N, int K,
-                        int lda, int ldb, int ldc, int oa, int ob,
-                        double al, double be, hipStream_t s) {
-  return gemm_tiles_v2_f64(d, n, A, B, C, M, N, K, lda, ldb, ldc, oa, ob, al,
-                           be, s);
-}
-template <>
-int v2_dispatch<float>(const GemmDesc* d, int n, const float* A,
-                       const float* B, float* C, int M, int N, int K, int lda,
-                       int ldb, int ldc, int oa, int ob, float al, float be,
-                       hipStream_t s) {
-  return gemm_tiles_v2_f32(d, n, A, B, C, M, N, K, lda, ldb, ldc, oa, ob, al,
-                           be, s);
+// The op-pair tables below are indexed [opA][opB] with the OP_* codes.
+template <typename T, int BN, bool GUARD>
+auto real_kernel(int oa, int ob) {
+#define K(OA, OB) gemm_tiles_k<T, OA, OB, BN, GUARD>
+  static constexpr decltype(&K(OP_N, OP_N)) table[2][2] = {
+      {K(OP_N, OP_N), K(OP_N, OP_T)}, {K(OP_T, OP_N), K(OP_T, OP_T)}};
+#undef K
+  return table[oa][ob];
 }
 
 template <typename T>
-void launch_real(const GemmDesc* descs, int ndesc, const T* A, const T* B, T* C,
-                 int M, int N, int K, int lda, int ldb, int ldc, int opA,
-                 int opB, T alpha, T beta, hipStream_t stream, int inplace) {
-  if (ndesc <= 0 || M <= 0 || N <= 0) return;
-  // v2 glds fast path for full-tile non-inplace batches (the hot phases)
-  if (!inplace &&
-      v2_dispatch<T>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc,
-                     (opA == OP_C) ? OP_T : opA, (opB == OP_C) ? OP_T : opB,
-                     alpha, beta, stream))
-    return;
-  // kernel variant (microbench lever): 0 = BK16 single-buffer (default),
-  // 1 = BK32 single-buffer, 2 = BK16 double-buffer (one barrier per step)
-  static const int variant = [] {
-    const char* v = getenv("DLAF_GEMM_VARIANT");
-    return v ? atoi(v) : 0;
-  }();
-  // N <= 64 is a single column block even at BN=64, hence in-place safe.
-  const int BN = (inplace && N > 64) ? 128 : 64;
-  const int mblocks = (M + 127) / 128, nblocks = (N + BN - 1) / BN;
-  const dim3 grid(ndesc * mblocks * nblocks);
-  const dim3 block(256);
-  // OP_C == OP_T for real scalars
-  const int oa = (opA == OP_C) ? OP_T : opA;
-  const int ob = (opB == OP_C) ? OP_T : opB;
-  static const int full_opt = [] {
-    const char* v = getenv("DLAF_GEMM_FULLOPT");
-    return v ? atoi(v) : 1;
-  }();
-  // NOTE: the guard-free test must use the TEMPLATE tile width (BNv), not
-  // the runtime BN: the inplace branch instantiates the 128-wide kernel even
-  // when the grid is sized with BN=64 (N <= 64), relying on the guards to
-  // mask columns >= N.
-  const bool fullMK = full_opt && (M % 128 == 0) && (K % 16 == 0);
-#define LAUNCH(OA, OB, BNv, BKv, DB)                                         \
-  do {                                                                       \
-    if (fullMK && (N % BNv == 0) && BKv == 16)                               \
-      gemm_tiles_k<T, OA, OB, BNv, BKv, DB, false><<<grid, block, 0,         \
-          stream>>>(descs, A, B, C, M, N, K, lda, ldb, ldc, alpha, beta,     \
-                    mblocks, nblocks);                                       \
-    else                                                                     \
-      gemm_tiles_k<T, OA, OB, BNv, BKv, DB, true><<<grid, block, 0,          \
-          stream>>>(descs, A, B, C, M, N, K, lda, ldb, ldc, alpha, beta,     \
-                    mblocks, nblocks);                                       \
-  } while (0)
-#define CASE(OA, OB)                                                        \
-  if (oa == OA && ob == OB) {                                               \
-    if (inplace) {                                                          \
-      if (variant == 1)                                                     \
-        LAUNCH(OA, OB, 128, 32, false);                                     \
-      else if (variant == 2)                                                \
-        LAUNCH(OA, OB, 128, 16, true);                                      \
-      else                                                                  \
-        LAUNCH(OA, OB, 128, 16, false);                                     \
-    } else {                                                                \
-      if (variant == 1)                                                     \
-        LAUNCH(OA, OB, 64, 32, false);                                      \
-      else if (variant == 2)                                                \
-        LAUNCH(OA, OB, 64, 16, true);                                       \
-      else                                                                  \
-        LAUNCH(OA, OB, 64, 16, false);                                      \
-    }                                                                       \
-    return;                                                                 \
-  }
-  CASE(OP_N, OP_N) CASE(OP_N, OP_T) CASE(OP_T, OP_N) CASE(OP_T, OP_T)
-#undef CASE
-#undef LAUNCH
-}
-
-template <typename T>
-int v2_dispatch_cplx(const GemmDesc* descs, int ndesc, const T* A, const T* B,
-                     T* C, int M, int N, int K, int lda, int ldb, int ldc,
-                     int opA, int opB, T ar, T ai, T br, T bi,
-                     hipStream_t stream);
-template <>
-int v2_dispatch_cplx<double>(const GemmDesc* d, int n, const double* A,
-                             const double* B, double* C, int M, int N, int K,
-                             int lda, int ldb, int ldc, int oa, int ob,
-                             double ar, double ai, double br, double bi,
-                             hipStream_t s) {
-  return gemm_tiles_v2_c128(d, n, A, B, C, M, N, K, lda, ldb, ldc, oa, ob, ar,
-                            ai, br, bi, s);
-}
-template <>
-int v2_dispatch_cplx<float>(const GemmDesc* d, int n, const float* A,
-                            const float* B, float* C, int M, int N, int K,
-                            int lda, int ldb, int ldc, int oa, int ob,
-                            float ar, float ai, float br, float bi,
-                            hipStream_t s) {
-  return gemm_tiles_v2_c64(d, n, A, B, C, M, N, K, lda, ldb, ldc, oa, ob, ar,
-                           ai, br, bi, s);
-}
-
-template <typename T>
-void launch_cplx(const GemmDesc* descs, int ndesc, const T* A, const T* B, T* C,
-                 int M, int N, int K, int lda, int ldb, int ldc, int opA,
-                 int opB, T ar, T ai, T br, T bi, hipStream_t stream) {
-  if (ndesc <= 0 || M <= 0 || N <= 0) return;
-  if (v2_dispatch_cplx<T>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc, opA,
-                          opB, ar, ai, br, bi, stream))
-    return;
-  const int mblocks = (M + 63) / 64, nblocks = (N + 63) / 64;
-  const dim3 grid(ndesc * mblocks * nblocks);
-  const dim3 block(256);
-#define CASE(OA, OB)                                                          \
-  if (opA == OA && opB == OB) {                                               \
-    gemm_tiles_cplx_k<T, OA, OB><<<grid, block, 0, stream>>>(                 \
-        descs, A, B, C, M, N, K, lda, ldb, ldc, ar, ai, br, bi, mblocks,      \
-        nblocks);                                                             \
-    return;                                                                   \
-  }
-  CASE(OP_N, OP_N) CASE(OP_N, OP_T) CASE(OP_N, OP_C)
-  CASE(OP_T, OP_N) CASE(OP_T, OP_T) CASE(OP_T, OP_C)
-  CASE(OP_C, OP_N) CASE(OP_C, OP_T) CASE(OP_C, OP_C)
-#undef CASE
+auto cplx_kernel(int oa, int ob) {
+#define K(OA, OB) gemm_tiles_cplx_k<T, OA, OB>
+  static constexpr decltype(&K(OP_N, OP_N)) table[3][3] = {
+      {K(OP_N, OP_N), K(OP_N, OP_T), K(OP_N, OP_C)},
+      {K(OP_T, OP_N), K(OP_T, OP_T), K(OP_T, OP_C)},
+      {K(OP_C, OP_N), K(OP_C, OP_T), K(OP_C, OP_C)}};
+#undef K
+  return table[oa][ob];
 }
 
 }  // namespace
 
-extern "C" {
-
-void gemm_tiles_f64(const GemmDesc* descs, int ndesc, const double* A,
-                    const double* B, double* C, int M, int N, int K, int lda,
-                    int ldb, int ldc, int opA, int opB, double alpha,
-                    double beta, hipStream_t stream, int inplace) {
-  launch_real<double>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc, opA, opB,
-                      alpha, beta, stream, inplace);
+template <typename T>
+void dlaf::gemm_tiles(const GemmDesc* descs, int ndesc, const T* A, const T* B,
+                      T* C, int M, int N, int K, int lda, int ldb, int ldc,
+                      int opA, int opB, T alpha, T beta, hipStream_t stream,
+                      int inplace) {
+  if (ndesc <= 0 || M <= 0 || N <= 0 || !valid_op(opA) || !valid_op(opB)) return;
+  // glds fast path for full-tile non-inplace batches (the hot phases)
+  if (!inplace && gemm_tiles_v2(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc,
+                                opA, opB, alpha, beta, stream))
+    return;
+  // OP_C == OP_T for real scalars
+  const int oa = (opA == OP_C) ? OP_T : opA;
+  const int ob = (opB == OP_C) ? OP_T : opB;
+  // In-place applies take the 128-wide block (N <= 128 is then one column
+  // block, see the kernel comment); its guard-free form needs full blocks.
+  // Everything else is BN=64, guarded: with v2 in front, a full-tile
+  // non-inplace batch arrives here only for K == 0, where the guarded kernel
+  // computes the same C = beta*C without touching A or B.
+  const int BN = inplace ? 128 : 64;
+  const bool full = inplace && M % 128 == 0 && N % 128 == 0 && K % 16 == 0;
+  const int mblocks = (M + 127) / 128, nblocks = (N + BN - 1) / BN;
+  const auto kern = !inplace ? real_kernel<T, 64, true>(oa, ob)
+                    : full   ? real_kernel<T, 128, false>(oa, ob)
+                             : real_kernel<T, 128, true>(oa, ob);
+  hipLaunchKernelGGL(kern, dim3(ndesc * mblocks * nblocks), dim3(256), 0,
+                     stream, descs, A, B, C, M, N, K, lda, ldb, ldc, alpha,
+                     beta, mblocks, nblocks);
 }
 
-void gemm_tiles_f32(const GemmDesc* descs, int ndesc, const float* A,
-                    const float* B, float* C, int M, int N, int K, int lda,
-                    int ldb, int ldc, int opA, int opB, float alpha, float beta,
-                    hipStream_t stream, int inplace) {
-  launch_real<float>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc, opA, opB,
-                     alpha, beta, stream, inplace);
+template <typename T>
+void dlaf::gemm_tiles(const GemmDesc* descs, int ndesc, const cplx<T>* A,
+                      const cplx<T>* B, cplx<T>* C, int M, int N, int K,
+                      int lda, int ldb, int ldc, int opA, int opB,
+                      cplx<T> alpha, cplx<T> beta, hipStream_t stream,
+                      int /*inplace*/) {
+  if (ndesc <= 0 || M <= 0 || N <= 0 || !valid_op(opA) || !valid_op(opB)) return;
+  if (gemm_tiles_v2(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc, opA, opB,
+                    alpha, beta, stream))
+    return;
+  const int mblocks = (M + 63) / 64, nblocks = (N + 63) / 64;
+  hipLaunchKernelGGL(cplx_kernel<T>(opA, opB),
+                     dim3(ndesc * mblocks * nblocks), dim3(256), 0, stream,
+                     descs, interleaved(A), interleaved(B), interleaved(C), M,
+                     N, K, lda, ldb, ldc, alpha.re, alpha.im, beta.re, beta.im,
+                     mblocks, nblocks);
 }
 
-void gemm_tiles_c128(const GemmDesc* descs, int ndesc, const double* A,
-                     const double* B, double* C, int M, int N, int K, int lda,
-                     int ldb, int ldc, int opA, int opB, double alpha_re,
-                     double alpha_im, double beta_re, double beta_im,
-                     hipStream_t stream) {
-  launch_cplx<double>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc, opA, opB,
-                      alpha_re, alpha_im, beta_re, beta_im, stream);
-}
-
-void gemm_tiles_c64(const GemmDesc* descs, int ndesc, const float* A,
-                    const float* B, float* C, int M, int N, int K, int lda,
-                    int ldb, int ldc, int opA, int opB, float alpha_re,
-                    float alpha_im, float beta_re, float beta_im,
-                    hipStream_t stream) {
-  launch_cplx<float>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc, opA, opB,
-                     alpha_re, alpha_im, beta_re, beta_im, stream);
-}
-
-}  // extern "C"
+#define INSTANTIATE(S)                                                        \
+  template void dlaf::gemm_tiles(const GemmDesc*, int, const S*, const S*, S*, \
+                                 int, int, int, int, int, int, int, int, S, S, \
+                                 hipStream_t, int);
+INSTANTIATE(double)
+INSTANTIATE(float)
+INSTANTIATE(cplx<double>)
+INSTANTIATE(cplx<float>)
+#undef INSTANTIATE

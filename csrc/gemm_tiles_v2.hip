@@ -1,10 +1,12 @@
-// Fused batched tile GEMM v2 for CDNA4 (gfx950) — full-tile fast path.
+// Fused batched tile GEMM for CDNA4 (gfx950) — the glds full-tile fast path
+// behind dlaf::gemm_tiles (gemm_tiles.hip holds the entry points and the
+// guarded kernels; gemm_common.h the shared Mfma<T> / xcd_remap).
 //
-// Round-2 rewrite of the v1 kernel driven by the round-1 ISA analysis
-// (profiles/gemm_isa_analysis.md): the v1 loop was a serial stage->compute
+// Written from the ISA analysis of the register-staged kernel
+// (profiles/gemm_isa_analysis.md): that loop was a serial stage->compute
 // structure with 8-byte global loads and ~650 addressing instructions per
-// 32 MFMA (MfmaUtil 57.5%). v2 fixes all three findings at once by staging
-// through LDS-DMA (`global_load_lds_dwordx4`, 16 B per lane):
+// 32 MFMA (MfmaUtil 57.5%). This kernel fixes all three findings at once by
+// staging through LDS-DMA (`global_load_lds_dwordx4`, 16 B per lane):
 //   * no register staging, no ds_write pass, no per-element address VALU —
 //     each 1024-B LDS row is ONE instruction with per-lane global addresses
 //     held in incremented registers;
@@ -12,40 +14,17 @@
 //     s+1 is issued before the MFMA block of step s, so its latency lands
 //     under the 4096-cycle f64 MFMA span;
 //   * 128x128 C blocks (4 waves, 64x64 per wave, 4x4 fragments of
-//     mfma_f64_16x16x4) double the flop:LDS-byte ratio of v1's 128x64.
+//     mfma_f64_16x16x4) double the flop:LDS-byte ratio of the 128x64 block.
+// Workgroup ids go through xcd_remap so one desc's blocks share an L2.
 //
-// Scope: full tiles only (M%128==0, N%128==0, K%16==0 real; 64/64/16
+// Scope: full tiles only (M%128==0, N%64==0, K%16==0 real; 64/64/16
 // complex), not in-place. Edge shapes and in-place panel applies stay on
-// the guarded v1 kernel (gemm_tiles.hip). Role parity: the per-tile gemm
-// of the reference (/root/reference/include/dlaf/blas/tile.h:352) — here
-// one launch covers a whole fused phase.
-#include "kernels.h"
-#include <type_traits>
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
+// the guarded kernels (gemm_tiles.hip). Role parity: the per-tile gemm of
+// the reference (include/dlaf/blas/tile.h) — here one launch covers a whole
+// fused phase.
+#include "gemm_common.h"
 
 namespace {
-
-template <typename T>
-struct MfmaV2;
-template <>
-struct MfmaV2<double> {
-  using acc_t = v4d;
-  static __device__ inline acc_t mma(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  // measured on gfx950 (tools/probe_mfma_f64.hip): D row = lk + 4*reg
-  static __device__ inline int acc_row(int lk, int r) { return lk + 4 * r; }
-};
-template <>
-struct MfmaV2<float> {
-  using acc_t = v4f;
-  static __device__ inline acc_t mma(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ inline int acc_row(int lk, int r) { return lk * 4 + r; }
-};
 
 __device__ inline void glds16(const void* g, void* lds) {
   __builtin_amdgcn_global_load_lds(
@@ -53,19 +32,10 @@ __device__ inline void glds16(const void* g, void* lds) {
       (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
 }
 
-// Bijective XCD remap (8 XCDs): consecutive output ids land on one XCD so
-// the blocks of one desc (which share A/B slabs) co-reside in one L2.
-__device__ inline int xcd_remap(int wg, int nwg) {
-  const int nx = 8;
-  const int q = nwg / nx, r = nwg % nx;
-  const int xcd = wg % nx, pos = wg / nx;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-}
-
 // ---------------- real kernel ----------------
 // BM=128 x BN (template 64/128), BK=16, 256 threads; 4 waves as a 2x2 grid
 // of (64 x BN/2) tiles; NFRAG = BN/32 fragments of mfma_{f64,f32}_16x16x4.
-// LDS (one __shared__ object — §5 trap 4a): S[DEPTH][A: 128*BK | B: BK*BN].
+// LDS (one __shared__ object — §5 trap 4a): S[2][A: 128*BK | B: BK*BN].
 //   A image: OPA==N -> row-major [i][k] (XOR chunk swizzle, below), else
 //   k-major [k][i]; B image: OPB==N -> k-major [k][c], else row-major
 //   [c][k] (swizzled). Images are glds-lane-linear: instr t covers LDS
@@ -76,12 +46,13 @@ __device__ inline int xcd_remap(int wg, int nwg) {
 // holds global chunk c ^ (row & (CPR-1)) — applied on the per-lane glds
 // SOURCE address (LDS stays lane-linear, the glds contract) and undone in
 // the fragment index; residual conflict is 2-way.
-template <typename T, int OPA, int OPB, int SWZ, int DEPTH, int BN,
-          int BK = 16, int BM = 128>
-__launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_k(
+template <typename T, int OPA, int OPB, int BN>
+__launch_bounds__(256, 2) __global__ void gemm_v2_k(
     const GemmDesc* __restrict__ descs, const T* __restrict__ A,
     const T* __restrict__ B, T* __restrict__ C, int M, int N, int K, int lda,
     int ldb, int ldc, T alpha, T beta, int mblocks, int nblocks) {
+  constexpr int BM = 128, BK = 16;
+  constexpr int DEPTH = 2;             // LDS ping-pong buffers
   constexpr int EPL = 16 / sizeof(T);  // elements per lane per glds
   constexpr int CPR = BK / EPL;        // 16-B chunks per rk-image row
   constexpr int AEL = BM * BK;         // A image elements
@@ -90,8 +61,7 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_k(
   constexpr int MFRAG = BM / 32;  // row frags per wave
   __shared__ T S[DEPTH][AEL + BEL];
 
-  int wg = blockIdx.x;
-  if constexpr (SWZ) wg = xcd_remap(wg, gridDim.x);
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int per_desc = mblocks * nblocks;
   const GemmDesc d = descs[wg / per_desc];
   const int rem = wg % per_desc;
@@ -108,7 +78,7 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_k(
   constexpr int NAW = AEL / (64 * EPL) / 4;
   constexpr int NBW = BEL / (64 * EPL) / 4;
 
-  using acc_t = typename MfmaV2<T>::acc_t;
+  using acc_t = typename Mfma<T>::acc_t;
   acc_t acc[MFRAG][NFRAG];
 #pragma unroll
   for (int a = 0; a < MFRAG; ++a)
@@ -217,33 +187,19 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_k(
       for (int mi = 0; mi < MFRAG; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NFRAG; ++ni)
-          acc[mi][ni] = MfmaV2<T>::mma(af[cur][mi], bf[cur][ni], acc[mi][ni]);
+          acc[mi][ni] = Mfma<T>::mma(af[cur][mi], bf[cur][ni], acc[mi][ni]);
     }
   };
 
-  // pipeline: DEPTH buffers, DEPTH-1 steps in flight. DEPTH==2 uses plain
-  // __syncthreads() (its vmcnt(0) drain IS the completion wait); DEPTH>=3
-  // uses counted per-wave vmcnt waits + raw barriers so DEPTH-2 steps stay
-  // in flight across each barrier (the guide's 3-buf span pattern).
-  constexpr int GPW = NAW + NBW;  // glds per wave per step
+  // pipeline: DEPTH buffers, DEPTH-1 steps in flight; the vmcnt(0) drain of
+  // __syncthreads() IS the completion wait.
   int ibuf = 0, cbuf = 0;
   for (int p = 0; p < DEPTH - 1 && p < total; ++p) {
     issue(ibuf);
     if (++ibuf == DEPTH) ibuf = 0;
   }
   for (int s = 0; s < total; ++s) {
-    if constexpr (DEPTH == 2) {
-      __syncthreads();  // drains the in-flight glds (vmcnt 0) + LDS reuse
-    } else {
-      const int rem_s = total - s - 1;  // steps still to land after this one
-      if (rem_s >= DEPTH - 2)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(GPW * (DEPTH - 2)) : "memory");
-      else if (rem_s == 1)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(GPW) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
+    __syncthreads();  // drains the in-flight glds (vmcnt 0) + LDS reuse
     if (s + DEPTH - 1 < total) {
       issue(ibuf);
       if (++ibuf == DEPTH) ibuf = 0;
@@ -265,7 +221,7 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_k(
       for (int ni = 0; ni < NFRAG; ++ni)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = i0 + wrow + mi * 16 + MfmaV2<T>::acc_row(lk, r);
+          const int row = i0 + wrow + mi * 16 + Mfma<T>::acc_row(lk, r);
           const int col = j0 + wcol + ni * 16 + li;
           cv[ni * 4 + r] = Cb[(int64_t)row * ldc + col];
         }
@@ -274,7 +230,7 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_k(
         const acc_t v = acc[mi][ni];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = i0 + wrow + mi * 16 + MfmaV2<T>::acc_row(lk, r);
+          const int row = i0 + wrow + mi * 16 + Mfma<T>::acc_row(lk, r);
           const int col = j0 + wcol + ni * 16 + li;
           Cb[(int64_t)row * ldc + col] = alpha * (T)v[r] + beta * cv[ni * 4 + r];
         }
@@ -288,7 +244,7 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_k(
         const acc_t v = acc[mi][ni];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = i0 + wrow + mi * 16 + MfmaV2<T>::acc_row(lk, r);
+          const int row = i0 + wrow + mi * 16 + Mfma<T>::acc_row(lk, r);
           const int col = j0 + wcol + ni * 16 + li;
           Cb[(int64_t)row * ldc + col] = alpha * (T)v[r];
         }
@@ -301,19 +257,19 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_k(
 // two). BM=BN=64, BK=16; wave w owns the 32x32 quadrant; 2x2 fragments,
 // 4 MFMA per fragment pair. LDS images mirror the real kernel with complex
 // elements; fragments are read as (re,im) pairs in one ds_read_b128 (f64).
-template <typename T, int OPA, int OPB, int SWZ, int DEPTH = 2>
-__launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_cplx_k(
+template <typename T, int OPA, int OPB>
+__launch_bounds__(256, 2) __global__ void gemm_v2_cplx_k(
     const GemmDesc* __restrict__ descs, const T* __restrict__ A,
     const T* __restrict__ B, T* __restrict__ C, int M, int N, int K, int lda,
     int ldb, int ldc, T alpha_re, T alpha_im, T beta_re, T beta_im,
     int mblocks, int nblocks) {
   constexpr int BK = 16;
+  constexpr int DEPTH = 2;            // LDS ping-pong buffers
   constexpr int CPL = 8 / sizeof(T);  // complex elems per lane per glds
   // S[buf][A: 64*16 | B: 16*64] complex elems, interleaved re/im
   __shared__ T S[DEPTH][4096 * (8 / sizeof(T))];
 
-  int wg = blockIdx.x;
-  if constexpr (SWZ) wg = xcd_remap(wg, gridDim.x);
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int per_desc = mblocks * nblocks;
   const GemmDesc d = descs[wg / per_desc];
   const int rem = wg % per_desc;
@@ -328,7 +284,7 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_cplx_k(
   const int total = (int)d.ktiles * spt;
   constexpr int NAW = 1024 / (64 * CPL) / 4;  // glds per wave (c128: 4, c64: 2)
 
-  using acc_t = typename MfmaV2<T>::acc_t;
+  using acc_t = typename Mfma<T>::acc_t;
   acc_t accr[2][2], acci[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
@@ -427,33 +383,21 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_cplx_k(
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
-          accr[mi][ni] = MfmaV2<T>::mma(ar[mi], br[ni], accr[mi][ni]);
-          accr[mi][ni] = MfmaV2<T>::mma(-ai[mi], bi_[ni], accr[mi][ni]);
-          acci[mi][ni] = MfmaV2<T>::mma(ar[mi], bi_[ni], acci[mi][ni]);
-          acci[mi][ni] = MfmaV2<T>::mma(ai[mi], br[ni], acci[mi][ni]);
+          accr[mi][ni] = Mfma<T>::mma(ar[mi], br[ni], accr[mi][ni]);
+          accr[mi][ni] = Mfma<T>::mma(-ai[mi], bi_[ni], accr[mi][ni]);
+          acci[mi][ni] = Mfma<T>::mma(ar[mi], bi_[ni], acci[mi][ni]);
+          acci[mi][ni] = Mfma<T>::mma(ai[mi], br[ni], acci[mi][ni]);
         }
     }
   };
 
-  constexpr int GPW = 2 * NAW;
   int ibuf = 0, cbuf = 0;
   for (int p = 0; p < DEPTH - 1 && p < total; ++p) {
     issue(ibuf);
     if (++ibuf == DEPTH) ibuf = 0;
   }
   for (int s = 0; s < total; ++s) {
-    if constexpr (DEPTH == 2) {
-      __syncthreads();
-    } else {
-      const int rem_s = total - s - 1;
-      if (rem_s >= DEPTH - 2)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(GPW * (DEPTH - 2)) : "memory");
-      else if (rem_s == 1)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(GPW) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
+    __syncthreads();
     if (s + DEPTH - 1 < total) {
       issue(ibuf);
       if (++ibuf == DEPTH) ibuf = 0;
@@ -471,7 +415,7 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_cplx_k(
       for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = i0 + wrow + mi * 16 + MfmaV2<T>::acc_row(lk, r);
+          const int row = i0 + wrow + mi * 16 + Mfma<T>::acc_row(lk, r);
           const int col = j0 + wcol + ni * 16 + li;
           const int64_t off = 2 * ((int64_t)row * ldc + col);
           cv[(ni * 4 + r) * 2] = Cb[off];
@@ -483,7 +427,7 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_cplx_k(
         const acc_t vi = acci[mi][ni];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = i0 + wrow + mi * 16 + MfmaV2<T>::acc_row(lk, r);
+          const int row = i0 + wrow + mi * 16 + Mfma<T>::acc_row(lk, r);
           const int col = j0 + wcol + ni * 16 + li;
           const int64_t off = 2 * ((int64_t)row * ldc + col);
           const T cr = cv[(ni * 4 + r) * 2], ci = cv[(ni * 4 + r) * 2 + 1];
@@ -503,7 +447,7 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_cplx_k(
         const acc_t vi = acci[mi][ni];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = i0 + wrow + mi * 16 + MfmaV2<T>::acc_row(lk, r);
+          const int row = i0 + wrow + mi * 16 + Mfma<T>::acc_row(lk, r);
           const int col = j0 + wcol + ni * 16 + li;
           const int64_t off = 2 * ((int64_t)row * ldc + col);
           Cb[off] = alpha_re * (T)vr[r] - alpha_im * (T)vi[r];
@@ -513,171 +457,71 @@ __launch_bounds__(256, DEPTH == 2 ? 2 : 1) __global__ void gemm_v2_cplx_k(
   }
 }
 
-template <typename T>
-int launch_v2_real(const GemmDesc* descs, int ndesc, const T* A, const T* B,
-                   T* C, int M, int N, int K, int lda, int ldb, int ldc,
-                   int opA, int opB, T alpha, T beta, hipStream_t stream) {
-  static const int bm_env = [] {
-    const char* v = getenv("DLAF_GEMM_V2_BM");
-    return v ? atoi(v) : 128;
-  }();
-  const int bm = (bm_env == 64 && M % 64 == 0) ? 64 : 128;
-  if (M % bm || N % 64 || K % 16 || K <= 0) return 0;  // BK=8 needs K%16 too
-  static const int enabled = [] {
-    const char* v = getenv("DLAF_GEMM_V2");
-    return v ? atoi(v) : 1;
-  }();
-  static const int swz = [] {
-    const char* v = getenv("DLAF_GEMM_V2_SWZ");
-    return v ? atoi(v) : 1;
-  }();
-  static const int depth = [] {
-    const char* v = getenv("DLAF_GEMM_V2_DEPTH");
-    const int d = v ? atoi(v) : 2;
-    return d < 2 ? 2 : (d > 3 ? 3 : d);
-  }();
-  static const int bn_env = [] {
-    const char* v = getenv("DLAF_GEMM_V2_BN");
-    return v ? atoi(v) : 128;
-  }();
-  static const int bk_env = [] {
-    const char* v = getenv("DLAF_GEMM_V2_BK");
-    return v ? atoi(v) : 16;
-  }();
-  if (!enabled) return 0;
-  const int bn = (N % bn_env == 0) ? bn_env : (N % 64 == 0 ? 64 : 128);
-  if (N % bn) return 0;
-  const int mblocks = M / bm, nblocks = N / bn;
-  const dim3 grid(ndesc * mblocks * nblocks);
-  const dim3 block(256);
-  const int oa = (opA == OP_C) ? OP_T : opA;
-  const int ob = (opB == OP_C) ? OP_T : opB;
-#define LV2(OA, OB, SW, DP, BNv)                                           \
-  gemm_v2_k<T, OA, OB, SW, DP, BNv><<<grid, block, 0, stream>>>(           \
-      descs, A, B, C, M, N, K, lda, ldb, ldc, alpha, beta, mblocks,        \
-      nblocks)
-#define LV2K(OA, OB, SW, DP, BNv, BKv)                                    \
-  gemm_v2_k<T, OA, OB, SW, DP, BNv, BKv><<<grid, block, 0, stream>>>(      \
-      descs, A, B, C, M, N, K, lda, ldb, ldc, alpha, beta, mblocks,        \
-      nblocks)
-#define LV2M(OA, OB, SW)                                                   \
-  gemm_v2_k<T, OA, OB, SW, 2, 128, 16, 64><<<grid, block, 0, stream>>>(    \
-      descs, A, B, C, M, N, K, lda, ldb, ldc, alpha, beta, mblocks,        \
-      nblocks)
-#define CASE(OA, OB)                                                       \
-  if (oa == OA && ob == OB) {                                              \
-    if (bm == 64) {                                                        \
-      if (N % 128) return 0;                                               \
-      if (swz) LV2M(OA, OB, 1); else LV2M(OA, OB, 0);                      \
-    } else if (bk_env == 8 && bn == 64) {                                         \
-      if (swz) LV2K(OA, OB, 1, 2, 64, 8); else LV2K(OA, OB, 0, 2, 64, 8);  \
-    } else if (bn == 64) {                                                 \
-      if (depth == 2) {                                                    \
-        if (swz) LV2(OA, OB, 1, 2, 64); else LV2(OA, OB, 0, 2, 64);        \
-      } else {                                                             \
-        if (swz) LV2(OA, OB, 1, 3, 64); else LV2(OA, OB, 0, 3, 64);        \
-      }                                                                    \
-    } else {                                                               \
-      if (depth == 2) {                                                    \
-        if (swz) LV2(OA, OB, 1, 2, 128); else LV2(OA, OB, 0, 2, 128);      \
-      } else {                                                             \
-        if (swz) LV2(OA, OB, 1, 3, 128); else LV2(OA, OB, 0, 3, 128);      \
-      }                                                                    \
-    }                                                                      \
-    return 1;                                                              \
-  }
-  CASE(OP_N, OP_N) CASE(OP_N, OP_T) CASE(OP_T, OP_N) CASE(OP_T, OP_T)
-#undef CASE
-#undef LV2M
-#undef LV2K
-#undef LV2
-  return 0;
+// The op-pair tables below are indexed [opA][opB] with the OP_* codes.
+template <typename T, int BN>
+auto real_kernel(int oa, int ob) {
+#define K(OA, OB) gemm_v2_k<T, OA, OB, BN>
+  static constexpr decltype(&K(OP_N, OP_N)) table[2][2] = {
+      {K(OP_N, OP_N), K(OP_N, OP_T)}, {K(OP_T, OP_N), K(OP_T, OP_T)}};
+#undef K
+  return table[oa][ob];
 }
 
 template <typename T>
-int launch_v2_cplx(const GemmDesc* descs, int ndesc, const T* A, const T* B,
-                   T* C, int M, int N, int K, int lda, int ldb, int ldc,
-                   int opA, int opB, T ar, T ai, T br, T bi,
-                   hipStream_t stream) {
-  if (M % 64 || N % 64 || K % 16 || K <= 0) return 0;
-  static const int enabled = [] {
-    const char* v = getenv("DLAF_GEMM_V2");
-    return v ? atoi(v) : 1;
-  }();
-  static const int swz = [] {
-    const char* v = getenv("DLAF_GEMM_V2_SWZ");
-    return v ? atoi(v) : 1;
-  }();
-  static const int depth = [] {
-    const char* v = getenv("DLAF_GEMM_V2_DEPTH");
-    const int d = v ? atoi(v) : 2;
-    return d < 2 ? 2 : (d > 4 ? 4 : d);
-  }();
-  if (!enabled) return 0;
-  const int mblocks = M / 64, nblocks = N / 64;
-  const dim3 grid(ndesc * mblocks * nblocks);
-  const dim3 block(256);
-#define LV2C(OA, OB, SW, DP)                                               \
-  gemm_v2_cplx_k<T, OA, OB, SW, DP><<<grid, block, 0, stream>>>(           \
-      descs, A, B, C, M, N, K, lda, ldb, ldc, ar, ai, br, bi, mblocks,     \
-      nblocks)
-#define CASE(OA, OB)                                                       \
-  if (opA == OA && opB == OB) {                                            \
-    if (depth == 2) {                                                      \
-      if (swz) LV2C(OA, OB, 1, 2); else LV2C(OA, OB, 0, 2);                \
-    } else if (depth == 3) {                                               \
-      if (swz) LV2C(OA, OB, 1, 3); else LV2C(OA, OB, 0, 3);                \
-    } else {                                                               \
-      if (swz) LV2C(OA, OB, 1, 4); else LV2C(OA, OB, 0, 4);                \
-    }                                                                      \
-    return 1;                                                              \
-  }
-  CASE(OP_N, OP_N) CASE(OP_N, OP_T) CASE(OP_N, OP_C)
-  CASE(OP_T, OP_N) CASE(OP_T, OP_T) CASE(OP_T, OP_C)
-  CASE(OP_C, OP_N) CASE(OP_C, OP_T) CASE(OP_C, OP_C)
-#undef CASE
-#undef LV2C
-  return 0;
+auto cplx_kernel(int oa, int ob) {
+#define K(OA, OB) gemm_v2_cplx_k<T, OA, OB>
+  static constexpr decltype(&K(OP_N, OP_N)) table[3][3] = {
+      {K(OP_N, OP_N), K(OP_N, OP_T), K(OP_N, OP_C)},
+      {K(OP_T, OP_N), K(OP_T, OP_T), K(OP_T, OP_C)},
+      {K(OP_C, OP_N), K(OP_C, OP_T), K(OP_C, OP_C)}};
+#undef K
+  return table[oa][ob];
 }
 
 }  // namespace
 
-extern "C" {
-
-int gemm_tiles_v2_f64(const GemmDesc* descs, int ndesc, const double* A,
-                      const double* B, double* C, int M, int N, int K, int lda,
-                      int ldb, int ldc, int opA, int opB, double alpha,
-                      double beta, hipStream_t stream) {
-  return launch_v2_real<double>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc,
-                                opA, opB, alpha, beta, stream);
+template <typename T>
+bool dlaf::gemm_tiles_v2(const GemmDesc* descs, int ndesc, const T* A,
+                         const T* B, T* C, int M, int N, int K, int lda,
+                         int ldb, int ldc, int opA, int opB, T alpha, T beta,
+                         hipStream_t stream) {
+  if (M % 128 || N % 64 || K % 16 || K <= 0) return false;
+  if (!valid_op(opA) || !valid_op(opB)) return false;
+  // OP_C == OP_T for real scalars
+  const int oa = (opA == OP_C) ? OP_T : opA;
+  const int ob = (opB == OP_C) ? OP_T : opB;
+  const int BN = (N % 128 == 0) ? 128 : 64;
+  const int mblocks = M / 128, nblocks = N / BN;
+  const auto kern =
+      BN == 128 ? real_kernel<T, 128>(oa, ob) : real_kernel<T, 64>(oa, ob);
+  hipLaunchKernelGGL(kern, dim3(ndesc * mblocks * nblocks), dim3(256), 0, stream,
+                     descs, A, B, C, M, N, K, lda, ldb, ldc, alpha, beta,
+                     mblocks, nblocks);
+  return true;
 }
 
-int gemm_tiles_v2_f32(const GemmDesc* descs, int ndesc, const float* A,
-                      const float* B, float* C, int M, int N, int K, int lda,
-                      int ldb, int ldc, int opA, int opB, float alpha,
-                      float beta, hipStream_t stream) {
-  return launch_v2_real<float>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc,
-                               opA, opB, alpha, beta, stream);
+template <typename T>
+bool dlaf::gemm_tiles_v2(const GemmDesc* descs, int ndesc, const cplx<T>* A,
+                         const cplx<T>* B, cplx<T>* C, int M, int N, int K,
+                         int lda, int ldb, int ldc, int opA, int opB,
+                         cplx<T> alpha, cplx<T> beta, hipStream_t stream) {
+  if (M % 64 || N % 64 || K % 16 || K <= 0) return false;
+  if (!valid_op(opA) || !valid_op(opB)) return false;
+  const int mblocks = M / 64, nblocks = N / 64;
+  hipLaunchKernelGGL(cplx_kernel<T>(opA, opB),
+                     dim3(ndesc * mblocks * nblocks), dim3(256), 0, stream,
+                     descs, interleaved(A), interleaved(B), interleaved(C), M,
+                     N, K, lda, ldb, ldc, alpha.re, alpha.im, beta.re, beta.im,
+                     mblocks, nblocks);
+  return true;
 }
 
-int gemm_tiles_v2_c128(const GemmDesc* descs, int ndesc, const double* A,
-                       const double* B, double* C, int M, int N, int K,
-                       int lda, int ldb, int ldc, int opA, int opB,
-                       double alpha_re, double alpha_im, double beta_re,
-                       double beta_im, hipStream_t stream) {
-  return launch_v2_cplx<double>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc,
-                                opA, opB, alpha_re, alpha_im, beta_re, beta_im,
-                                stream);
-}
-
-int gemm_tiles_v2_c64(const GemmDesc* descs, int ndesc, const float* A,
-                      const float* B, float* C, int M, int N, int K, int lda,
-                      int ldb, int ldc, int opA, int opB, float alpha_re,
-                      float alpha_im, float beta_re, float beta_im,
-                      hipStream_t stream) {
-  return launch_v2_cplx<float>(descs, ndesc, A, B, C, M, N, K, lda, ldb, ldc,
-                               opA, opB, alpha_re, alpha_im, beta_re, beta_im,
-                               stream);
-}
-
-}  // extern "C"
+#define INSTANTIATE(S)                                                     \
+  template bool dlaf::gemm_tiles_v2(const GemmDesc*, int, const S*,        \
+                                    const S*, S*, int, int, int, int, int, \
+                                    int, int, int, S, S, hipStream_t);
+INSTANTIATE(double)
+INSTANTIATE(float)
+INSTANTIATE(cplx<double>)
+INSTANTIATE(cplx<float>)
+#undef INSTANTIATE

@@ -1,13 +1,21 @@
-// Shared declarations between the HIP kernel TUs and the torch extension TU.
+// Every native entry point of the extension, declared once.
 //
 // Design (see SURVEY.md §2.4/§2.5 for the reference per-tile op inventory this
 // replaces): instead of one kernel launch per tile task, the hot ops are FUSED —
 // one launch processes a whole list of tile-triples described by GemmDesc records,
 // so a full trailing update / panel solve / back-transform sweep is a single
 // kernel with >> 256 workgroups (MI355X: 256 CUs over 8 XCDs).
+//
+// Entry points are templates on the element type S: double, float,
+// cplx<double>, cplx<float> (cplx.h; layout-identical to torch's interleaved
+// complex). Each is defined in its .hip file under its qualified name
+// (`dlaf::name`) and explicitly instantiated there, so a definition that
+// drifts from the declaration here fails to compile.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+
+#include "cplx.h"
 
 // op codes (match dlaf_amd.types.Op encoding used by the Python layer)
 #define OP_N 0
@@ -26,89 +34,85 @@ struct GemmDesc {
   int64_t b_kstride;  // element stride between consecutive K tiles of B
 };
 
-extern "C" {
+namespace dlaf {
 
-// ---- fused batched GEMM (MFMA f64 / f32) ----
+// Diagonal-block size of the tile Cholesky (dinv blocks are kPotrfBsz^2).
+// 64 for every dtype: the fused factor+invert kernel then needs ~73 KiB LDS
+// and can co-reside with trailing-update GEMM blocks on a CU — a 128-block
+// (160 KiB) kernel can never be scheduled next to them and serializes the
+// lookahead.
+constexpr int kPotrfBsz = 64;
+
+// ---- fused batched GEMM (MFMA f64 / f32), csrc/gemm_tiles.hip ----
 // C (M x N, ldc), op(A) (M x K), op(B) (K x N); K is the per-tile K extent.
-// `inplace` selects the wide-BN instantiation that makes X = X*op(B) safe in
-// place (C block == A block); required whenever C aliases A.
-void gemm_tiles_f64(const GemmDesc* descs, int ndesc, const double* A,
-                    const double* B, double* C, int M, int N, int K, int lda,
-                    int ldb, int ldc, int opA, int opB, double alpha,
-                    double beta, hipStream_t stream, int inplace);
-void gemm_tiles_f32(const GemmDesc* descs, int ndesc, const float* A,
-                    const float* B, float* C, int M, int N, int K, int lda,
-                    int ldb, int ldc, int opA, int opB, float alpha, float beta,
-                    hipStream_t stream, int inplace);
-// complex variants (interleaved re/im); opA/opB support OP_C (conjugate).
-void gemm_tiles_c128(const GemmDesc* descs, int ndesc, const double* A,
-                     const double* B, double* C, int M, int N, int K, int lda,
-                     int ldb, int ldc, int opA, int opB, double alpha_re,
-                     double alpha_im, double beta_re, double beta_im,
-                     hipStream_t stream);
-void gemm_tiles_c64(const GemmDesc* descs, int ndesc, const float* A,
-                    const float* B, float* C, int M, int N, int K, int lda,
-                    int ldb, int ldc, int opA, int opB, float alpha_re,
-                    float alpha_im, float beta_re, float beta_im,
+// Full-tile, non-aliased batches run on the glds kernel (gemm_tiles_v2),
+// everything else on the guarded register-staged kernel. Real S: OP_C == OP_T,
+// and `inplace` selects the wide-BN instantiation that makes X = X*op(B) safe
+// in place (C block == A block); required whenever C aliases A.
+template <typename T>
+void gemm_tiles(const GemmDesc* descs, int ndesc, const T* A, const T* B, T* C,
+                int M, int N, int K, int lda, int ldb, int ldc, int opA,
+                int opB, T alpha, T beta, hipStream_t stream, int inplace);
+// Complex S (opA/opB support OP_C). `inplace` is accepted and ignored: a 64x64
+// block per workgroup is in-place safe only while N <= 64, which the Python
+// layer guarantees by staging A otherwise (tile_ops.gemm_fused).
+template <typename T>
+void gemm_tiles(const GemmDesc* descs, int ndesc, const cplx<T>* A,
+                const cplx<T>* B, cplx<T>* C, int M, int N, int K, int lda,
+                int ldb, int ldc, int opA, int opB, cplx<T> alpha, cplx<T> beta,
+                hipStream_t stream, int inplace);
+
+// ---- glds full-tile fast path, csrc/gemm_tiles_v2.hip ----
+// Launches and returns true when the shape qualifies (real: M%128, N%64,
+// K%16 all zero; complex: M%64, N%64, K%16; K > 0); else returns false and
+// launches nothing. C must not alias A or B.
+template <typename T>
+bool gemm_tiles_v2(const GemmDesc* descs, int ndesc, const T* A, const T* B,
+                   T* C, int M, int N, int K, int lda, int ldb, int ldc,
+                   int opA, int opB, T alpha, T beta, hipStream_t stream);
+template <typename T>
+bool gemm_tiles_v2(const GemmDesc* descs, int ndesc, const cplx<T>* A,
+                   const cplx<T>* B, cplx<T>* C, int M, int N, int K, int lda,
+                   int ldb, int ldc, int opA, int opB, cplx<T> alpha,
+                   cplx<T> beta, hipStream_t stream);
+
+// ---- bt window-chain group apply (one launch per sweep group), bt_apply.hip
+// S = double or cplx<double>. Returns false when (b, G, R) has no kernel.
+template <typename S>
+bool bt_apply_group(S* E, int64_t nE, int64_t npad, const S* V, const S* VTt,
+                    int64_t base0, int b, int G, int R, int nwin,
                     hipStream_t stream);
 
-// ---- fused batched GEMM v2 (full-tile glds fast path; returns 1 if taken) ----
-int gemm_tiles_v2_f64(const GemmDesc* descs, int ndesc, const double* A,
-                      const double* B, double* C, int M, int N, int K, int lda,
-                      int ldb, int ldc, int opA, int opB, double alpha,
-                      double beta, hipStream_t stream);
-int gemm_tiles_v2_f32(const GemmDesc* descs, int ndesc, const float* A,
-                      const float* B, float* C, int M, int N, int K, int lda,
-                      int ldb, int ldc, int opA, int opB, float alpha,
-                      float beta, hipStream_t stream);
-int gemm_tiles_v2_c128(const GemmDesc* descs, int ndesc, const double* A,
-                       const double* B, double* C, int M, int N, int K,
-                       int lda, int ldb, int ldc, int opA, int opB,
-                       double alpha_re, double alpha_im, double beta_re,
-                       double beta_im, hipStream_t stream);
-int gemm_tiles_v2_c64(const GemmDesc* descs, int ndesc, const float* A,
-                      const float* B, float* C, int M, int N, int K, int lda,
-                      int ldb, int ldc, int opA, int opB, float alpha_re,
-                      float alpha_im, float beta_re, float beta_im,
-                      hipStream_t stream);
-
-// ---- bt window-chain group apply (one launch per sweep group) ----
-int bt_apply_group_f64(double* E, int64_t nE, int64_t npad, const double* V,
-                       const double* VTt, int64_t base0, int b, int G, int R,
-                       int nwin, hipStream_t stream);
-int bt_apply_group_c128(double* E, int64_t nE, int64_t npad, const double* V,
-                        const double* VTt, int64_t base0, int b, int G, int R,
-                        int nwin, hipStream_t stream);
-
-// ---- single-tile factorization building blocks ----
+// ---- single-tile factorization building blocks, csrc/factor.hip ----
 // Fused single-workgroup [factor +] invert of one diagonal block: factors the
-// leading n x n (if do_factor) in place and writes its inverse into the
-// BSZ x BSZ block Tout (BSZ = 128 real / 64 complex; identity-extended).
-void potrf_invert_block_f64(double* A, int n, int ld, double* Tout,
-                            int do_factor, hipStream_t stream);
-void potrf_invert_block_f32(float* A, int n, int ld, float* Tout,
-                            int do_factor, hipStream_t stream);
-void potrf_invert_block_c128(double* A, int n, int ld, double* Tout,
-                             int do_factor, hipStream_t stream);
-void potrf_invert_block_c64(float* A, int n, int ld, float* Tout,
-                            int do_factor, hipStream_t stream);
+// leading n x n (n <= kPotrfBsz, if do_factor) in place and writes its inverse
+// into the kPotrfBsz x kPotrfBsz block Tout (identity-extended).
+template <typename S>
+void potrf_invert_block(S* A, int n, int ld, S* Tout, int do_factor,
+                        hipStream_t stream);
 
-// In-place Cholesky (Lower) of the leading n x n (n <= 128) of a tile with row
-// stride ld; single workgroup, LDS-resident.
-void potrf_block128_f64(double* A, int n, int ld, hipStream_t stream);
-void potrf_block128_f32(float* A, int n, int ld, hipStream_t stream);
-void potrf_block128_c128(double* A, int n, int ld, hipStream_t stream);
-void potrf_block128_c64(float* A, int n, int ld, hipStream_t stream);
+// Column-parallel inverse of a lower-triangular n x n block (arbitrary n;
+// single LDS-resident workgroup when it fits): T = L^-1, T may not alias L.
+template <typename S>
+void trtri_lower(const S* L, S* T, int n, int ldl, int ldt, int unit_diag,
+                 hipStream_t stream);
 
-// Column-parallel inverse of a lower-triangular n x n block (n <= 128 per
-// workgroup column count; arbitrary n supported): T = L^-1, T may not alias L.
-void trtri_lower_f64(const double* L, double* T, int n, int ldl, int ldt,
-                     int unit_diag, hipStream_t stream);
-void trtri_lower_f32(const float* L, float* T, int n, int ldl, int ldt,
-                     int unit_diag, hipStream_t stream);
-void trtri_lower_c128(const double* L, double* T, int n, int ldl, int ldt,
-                      int unit_diag, hipStream_t stream);
-void trtri_lower_c64(const float* L, float* T, int n, int ldl, int ldt,
-                     int unit_diag, hipStream_t stream);
+// ---- GPU bulge chase band -> tridiagonal, csrc/chase_gpu.hip ----
+template <typename S>
+void chase_gpu(S* a, int64_t ld, int64_t size, int64_t b, S* vstore,
+               const int64_t* offsets, int32_t* done, int32_t* abortf,
+               hipStream_t stream);
 
-}  // extern "C"
+// ---- cooperative whole-panel QR, csrc/panel_qr.hip ----
+// Returns 0 on success, else the hipError of the cooperative launch.
+// norms/wraw must be zeroed by the caller.
+template <typename S>
+int panel_qr(S* P, long m, int nb, long ldp, S* taus,
+             typename ScalarTraits<S>::real_t* norms, S* wraw,
+             hipStream_t stream);
+
+// ---- D&C secular-equation roots, csrc/secular.hip ----
+void secular_roots(const double* d, const double* z2, int k, double rho,
+                   long long* sidx, double* mu, hipStream_t stream);
+
+}  // namespace dlaf

@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_cooperative_groups.h>
 
-#include "cplx.h"
+#include "kernels.h"
 
 namespace cg = cooperative_groups;
 
@@ -261,44 +261,43 @@ int32_t* sync_workspace() {
 }
 }  // namespace
 
-extern "C" {
-
 // Launch helper; returns 0 on success. norms/wraw must be zeroed by caller.
-#define DEF_PANEL_QR(SUF, T, R)                                               \
-  int panel_qr_##SUF(T* P, long m, int nb, long ldp, T* taus, R* norms,       \
-                     T* wraw, hipStream_t stream) {                           \
-    int threads = 256;                                                        \
-    hipDeviceProp_t prop;                                                     \
-    int dev_ = 0;                                                             \
-    (void)hipGetDevice(&dev_);                                                \
-    (void)hipGetDeviceProperties(&prop, dev_);                                \
-    int per_cu = 0;                                                           \
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(                       \
-        &per_cu, reinterpret_cast<const void*>(&panel_qr_kernel<T>), threads, \
-        0);                                                                   \
-    int blocks = prop.multiProcessorCount * (per_cu > 0 ? per_cu : 1);        \
-    /* cap chosen when the cg grid.sync cost grew with WG count; the agent  \
-       counter barrier is cheap at 256 WGs so a higher cap may now win —    \
-       tunable via DLAF_PANEL_QR_BLOCKS (256 untested at scale)             */ \
-    static const int cap = [] {                                               \
-      const char* v = getenv("DLAF_PANEL_QR_BLOCKS");                         \
-      return v ? atoi(v) : 128;                                               \
-    }();                                                                      \
-    if (blocks > cap) blocks = cap;                                           \
-    int32_t* sync_ws = sync_workspace();                                      \
-    if (!sync_ws) return (int)hipErrorOutOfMemory;                            \
-    void* args[] = {(void*)&P,    (void*)&m,     (void*)&nb,  (void*)&ldp,    \
-                    (void*)&taus, (void*)&norms, (void*)&wraw,                \
-                    (void*)&sync_ws};                                         \
-    hipError_t err = hipLaunchCooperativeKernel(                              \
-        reinterpret_cast<void*>(&panel_qr_kernel<T>), dim3(blocks),           \
-        dim3(threads), args, 0, stream);                                      \
-    return err == hipSuccess ? 0 : (int)err;                                  \
-  }
+template <typename T>
+int dlaf::panel_qr(T* P, long m, int nb, long ldp, T* taus,
+                   typename ScalarTraits<T>::real_t* norms, T* wraw,
+                   hipStream_t stream) {
+  int threads = 256;
+  hipDeviceProp_t prop;
+  int dev_ = 0;
+  (void)hipGetDevice(&dev_);
+  (void)hipGetDeviceProperties(&prop, dev_);
+  int per_cu = 0;
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &per_cu, reinterpret_cast<const void*>(&panel_qr_kernel<T>), threads, 0);
+  int blocks = prop.multiProcessorCount * (per_cu > 0 ? per_cu : 1);
+  // cap chosen when the cg grid.sync cost grew with WG count; the agent
+  // counter barrier is cheap at 256 WGs so a higher cap may now win —
+  // tunable via DLAF_PANEL_QR_BLOCKS (256 untested at scale)
+  static const int cap = [] {
+    const char* v = getenv("DLAF_PANEL_QR_BLOCKS");
+    return v ? atoi(v) : 128;
+  }();
+  if (blocks > cap) blocks = cap;
+  int32_t* sync_ws = sync_workspace();
+  if (!sync_ws) return (int)hipErrorOutOfMemory;
+  void* args[] = {(void*)&P,    (void*)&m,     (void*)&nb,  (void*)&ldp,
+                  (void*)&taus, (void*)&norms, (void*)&wraw, (void*)&sync_ws};
+  hipError_t err = hipLaunchCooperativeKernel(
+      reinterpret_cast<void*>(&panel_qr_kernel<T>), dim3(blocks),
+      dim3(threads), args, 0, stream);
+  return err == hipSuccess ? 0 : (int)err;
+}
 
-DEF_PANEL_QR(f64, double, double)
-DEF_PANEL_QR(f32, float, float)
-DEF_PANEL_QR(c128, cplx<double>, double)
-DEF_PANEL_QR(c64, cplx<float>, float)
-
-}  // extern "C"
+#define INSTANTIATE(S)                                             \
+  template int dlaf::panel_qr(S*, long, int, long, S*,             \
+                              ScalarTraits<S>::real_t*, S*, hipStream_t);
+INSTANTIATE(double)
+INSTANTIATE(float)
+INSTANTIATE(cplx<double>)
+INSTANTIATE(cplx<float>)
+#undef INSTANTIATE

@@ -15,6 +15,8 @@
 
 #include <cmath>
 
+#include "kernels.h"
+
 namespace {
 
 template <class T>
@@ -269,10 +271,8 @@ __global__ __launch_bounds__(256) void secular_wave_kernel(
 
 }  // namespace
 
-extern "C" {
-
-void secular_roots_f64(const double* d, const double* z2, int k, double rho,
-                       long long* sidx, double* mu, hipStream_t stream) {
+void dlaf::secular_roots(const double* d, const double* z2, int k, double rho,
+                         long long* sidx, double* mu, hipStream_t stream) {
   if (k <= 0) return;
   if (k >= 128) {
     // wave per root: 4 roots per 256-thread workgroup (a thread-per-root
@@ -286,5 +286,3 @@ void secular_roots_f64(const double* d, const double* z2, int k, double rho,
   const int blocks = (k + threads - 1) / threads;
   secular_kernel<double><<<blocks, threads, 0, stream>>>(d, z2, k, rho, sidx, mu);
 }
-
-}  // extern "C"

@@ -20,8 +20,9 @@ MI355X-native differences from the reference:
   transposed row panel is per-tile broadcasts along the column direction
   (reference ``broadcast_panel.h:78-189`` semantics).
 
-Only UpLo.Lower is implemented (the reference's miniapps and C API default);
-Upper can be added by symmetry.
+Lower is described above; local Upper (A = U^H U) runs natively on
+upper-stored tiles (``_cholesky_local_upper``) and distributed Upper goes
+through a storage transpose to the Lower path.
 """
 
 from __future__ import annotations
@@ -60,18 +61,6 @@ def _compute_dinv(diag: torch.Tensor, dinv: torch.Tensor) -> torch.Tensor:
         bs = min(bsz, nb - c0)
         ext.factor_invert_block(diag[c0:, c0:], bs, diag.stride(0), dinv[d], False)
     return dinv
-
-
-def _rows6(c, a, b, kt=1, aks=0, bks=0) -> np.ndarray:
-    n = len(c)
-    out = np.empty((n, 6), dtype=np.int64)
-    out[:, 0] = c
-    out[:, 1] = a
-    out[:, 2] = b
-    out[:, 3] = kt
-    out[:, 4] = aks
-    out[:, 5] = bks
-    return out
 
 
 class _DescTable:
@@ -125,8 +114,8 @@ def _trsm_plan_rows(table: _DescTable, key_prefix, offs: np.ndarray, nb: int,
     for d in range(nblocks):
         c0 = d * bsz
         if d > 0:
-            table.add((key_prefix, "trsm_upd", d), _rows6(offs + c0, offs, np.full(len(offs), c0 * ld_l)))
-        table.add((key_prefix, "trsm_apply", d), _rows6(offs + c0, offs + c0, np.zeros(len(offs), dtype=np.int64)))
+            table.add((key_prefix, "trsm_upd", d), ops.make_descs(offs + c0, offs, np.full(len(offs), c0 * ld_l)))
+        table.add((key_prefix, "trsm_apply", d), ops.make_descs(offs + c0, offs + c0, np.zeros(len(offs), dtype=np.int64)))
 
 
 def _run_trsm_panel(table: _DescTable, key_prefix, base: torch.Tensor,
@@ -177,8 +166,9 @@ def _local_plan(mat: Matrix) -> _DescTable:
                         c.append(mat.tile_offset((i, j)))
                         a.append(mat.tile_offset((i, k)))
                         b.append(mat.tile_offset((j, k)))
-                return _rows6(np.array(c, dtype=np.int64), np.array(a, dtype=np.int64),
-                              np.array(b, dtype=np.int64)) if c else None
+                return ops.make_descs(np.array(c, dtype=np.int64),
+                                      np.array(a, dtype=np.int64),
+                                      np.array(b, dtype=np.int64)) if c else None
             h = _descs_for([k + 1])
             if h is not None:
                 table.add(("k", k, "head"), h)
@@ -224,13 +214,13 @@ def _cholesky_local(mat: Matrix) -> None:
                     if k >= 1 and ev_tail[k - 1] is not None:
                         sp.wait_event(ev_tail[k - 1])
                     ops.gemm_fused(st, st, st, head, nb, nb, nb, nb, nb, nb,
-                                   Op.NoTrans, opc, -1.0, 1.0, uniform=True)
+                                   Op.NoTrans, opc, -1.0, 1.0)
             tail = table.get(("k", k, "tail"))
             if tail is not None:
                 with torch.cuda.stream(su):
                     su.wait_event(ev_p)
                     ops.gemm_fused(st, st, st, tail, nb, nb, nb, nb, nb, nb,
-                                   Op.NoTrans, opc, -1.0, 1.0, uniform=True)
+                                   Op.NoTrans, opc, -1.0, 1.0)
                     ev = torch.cuda.Event()
                     ev.record(su)
                     ev_tail[k] = ev
@@ -273,12 +263,12 @@ def _upper_plan(mat: Matrix) -> _DescTable:
                 c0 = dd * bsz
                 if dd > 0:
                     table.add(("Uk", k, "upd", dd),
-                              _rows6(offs + c0 * nb,
-                                     np.full(len(offs), c0 * nb), offs))
+                              ops.make_descs(offs + c0 * nb,
+                                             np.full(len(offs), c0 * nb), offs))
                 table.add(("Uk", k, "apply", dd),
-                          _rows6(offs + c0 * nb,
-                                 np.zeros(len(offs), dtype=np.int64),
-                                 np.arange(len(offs), dtype=np.int64) * (bsz * nb)))
+                          ops.make_descs(offs + c0 * nb,
+                                         np.zeros(len(offs), dtype=np.int64),
+                                         np.arange(len(offs), dtype=np.int64) * (bsz * nb)))
 
             def _descs_for(i_range):
                 c, a, b = [], [], []
@@ -287,9 +277,9 @@ def _upper_plan(mat: Matrix) -> _DescTable:
                         c.append(mat.tile_offset((i, j)))
                         a.append(mat.tile_offset((k, i)))
                         b.append(mat.tile_offset((k, j)))
-                return _rows6(np.array(c, dtype=np.int64),
-                              np.array(a, dtype=np.int64),
-                              np.array(b, dtype=np.int64)) if c else None
+                return ops.make_descs(np.array(c, dtype=np.int64),
+                                      np.array(a, dtype=np.int64),
+                                      np.array(b, dtype=np.int64)) if c else None
             h = _descs_for([k + 1])
             if h is not None:
                 table.add(("Uk", k, "head"), h)
@@ -424,9 +414,9 @@ def _dist_plan(mat: Matrix) -> _DescTable:
                 dst[1].append(li * ts)
                 dst[2].append(lj * ts)
         if ch:
-            table.add(("k", k, "head"), _rows6(np.array(ch), np.array(ah), np.array(bh)))
+            table.add(("k", k, "head"), ops.make_descs(np.array(ch), np.array(ah), np.array(bh)))
         if c:
-            table.add(("k", k, "trail"), _rows6(np.array(c), np.array(a), np.array(b)))
+            table.add(("k", k, "trail"), ops.make_descs(np.array(c), np.array(a), np.array(b)))
     table.upload(mat.device)
     _PLAN_CACHE[key] = table
     return table
@@ -576,16 +566,14 @@ def _cholesky_dist_gpu(mat: Matrix, grid: CommGrid) -> None:
             head = table.get(("k", k, "head"))
             if head is not None:
                 ops.gemm_fused(mat.storage, col_panel.storage, row_panel.storage, head,
-                               nb, nb, nb, nb, nb, nb, Op.NoTrans, opc, -1.0, 1.0,
-                               uniform=True)
+                               nb, nb, nb, nb, nb, nb, Op.NoTrans, opc, -1.0, 1.0)
             e = torch.cuda.Event()
             e.record(su)
             ev_head[k] = e
             tail = table.get(("k", k, "trail"))
             if tail is not None:
                 ops.gemm_fused(mat.storage, col_panel.storage, row_panel.storage, tail,
-                               nb, nb, nb, nb, nb, nb, Op.NoTrans, opc, -1.0, 1.0,
-                               uniform=True)
+                               nb, nb, nb, nb, nb, nb, Op.NoTrans, opc, -1.0, 1.0)
             e2 = torch.cuda.Event()
             e2.record(su)
             ev_tail[k] = e2

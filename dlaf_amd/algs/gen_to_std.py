@@ -119,7 +119,7 @@ def generalized_to_standard(uplo: UpLo, mat_a: Matrix, mat_l: Matrix,
                               mat_a.tile_offset((k, d.global_tile_of_local((0, lj))[1])))
                              for lj in range(lj_prev)]
                     ops.gemm_items(rowpAp.storage, linv, mat_a.storage, items, nb,
-                                   Op.NoTrans, Op.NoTrans, 1.0, 0.0, uniform=True)
+                                   Op.NoTrans, Op.NoTrans, 1.0, 0.0)
                     lrk = d.local_tile_of_global((k, d.global_tile_of_local((0, 0))[1]))[0]
                     mat_a.storage[lrk, :lj_prev].copy_(rowpAp.storage[:lj_prev])
                 else:
@@ -135,7 +135,7 @@ def generalized_to_standard(uplo: UpLo, mat_a: Matrix, mat_l: Matrix,
             items = [(mat_a.local_tile_offset(li, lj), colpL.offset(li), rowpAp.offset(lj))
                      for li in range(li0, lr) for lj in range(lj_prev)]
             ops.gemm_items(mat_a.storage, colpL.storage, rowpAp.storage, items, nb,
-                           Op.NoTrans, Op.NoTrans, -1.0, 1.0, uniform=True)
+                           Op.NoTrans, Op.NoTrans, -1.0, 1.0)
 
         # 2) diagonal tile transform
         if (d.rank_row, d.rank_col) == (kr, kc):
@@ -157,7 +157,7 @@ def generalized_to_standard(uplo: UpLo, mat_a: Matrix, mat_l: Matrix,
             hA = _herm_full(Akk, lower=True)
             ops.gemm_items(mat_a.storage, mat_l.storage, hA,
                            [(o, lo, 0) for o, lo in zip(offs, loffs)], nb,
-                           Op.NoTrans, Op.NoTrans, -0.5, 1.0, uniform=True)
+                           Op.NoTrans, Op.NoTrans, -0.5, 1.0)
         # broadcast the updated A panel (direct + transposed)
         pan.bcast_col_panel(mat_a, g, k, li0, lr, colpA)
         pan.transpose_col_to_row(d, g, colpA, rowpA, lj0, lc)
@@ -171,9 +171,9 @@ def generalized_to_standard(uplo: UpLo, mat_a: Matrix, mat_l: Matrix,
         trip_a = [(c, colpA.offset(li), rowpL.offset(lj)) for c, li, lj in items]
         trip_l = [(c, colpL.offset(li), rowpA.offset(lj)) for c, li, lj in items]
         ops.gemm_items(mat_a.storage, colpA.storage, rowpL.storage, trip_a, nb,
-                       Op.NoTrans, opc, -1.0, 1.0, uniform=True)
+                       Op.NoTrans, opc, -1.0, 1.0)
         ops.gemm_items(mat_a.storage, colpL.storage, rowpA.storage, trip_l, nb,
-                       Op.NoTrans, opc, -1.0, 1.0, uniform=True)
+                       Op.NoTrans, opc, -1.0, 1.0)
 
         # 5) second -1/2 L[:,k] A[k,k] correction
         if d.rank_col == kc and li0 < lr:
@@ -184,7 +184,7 @@ def generalized_to_standard(uplo: UpLo, mat_a: Matrix, mat_l: Matrix,
                      for li in range(li0, lr)]
             ops.gemm_items(mat_a.storage, mat_l.storage, hA,
                            [(o, lo, 0) for o, lo in zip(offs, loffs)], nb,
-                           Op.NoTrans, Op.NoTrans, -0.5, 1.0, uniform=True)
+                           Op.NoTrans, Op.NoTrans, -0.5, 1.0)
 
 
 def _herm_full_u(t: torch.Tensor) -> torch.Tensor:

@@ -149,7 +149,7 @@ def triangular_inverse(uplo: UpLo, diag: Diag, mat: Matrix,
                      for li in range(li0, lr)]
                 items = list(zip(c, [acc.offset(li) for li in range(li0, lr)], [0] * len(c)))
                 ops.gemm_items(mat.storage, acc.storage, inv, items, nb,
-                               Op.NoTrans, Op.NoTrans, -1.0, 0.0, uniform=True)
+                               Op.NoTrans, Op.NoTrans, -1.0, 0.0)
             kr = d.rank_of_tile_row(k)
             if d.rank_row == kr:
                 mat.tile((k, k)).copy_(inv)
@@ -317,6 +317,6 @@ def inverse_from_cholesky_factor(uplo: UpLo, mat: Matrix,
                 trip = (mat.local_tile_offset(li, lj), colpX.offset(li), rowpX.offset(lj))
                 (first if i == k else accum).append(trip)
         ops.gemm_items(mat.storage, colpX.storage, rowpX.storage, first, nb,
-                       opc, Op.NoTrans, 1.0, 0.0, uniform=True)
+                       opc, Op.NoTrans, 1.0, 0.0)
         ops.gemm_items(mat.storage, colpX.storage, rowpX.storage, accum, nb,
-                       opc, Op.NoTrans, 1.0, 1.0, uniform=True)
+                       opc, Op.NoTrans, 1.0, 1.0)

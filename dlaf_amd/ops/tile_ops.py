@@ -1,8 +1,11 @@
 """Mid-level tile operations with CPU (torch) / GPU (native HIP) dispatch.
 
 The GPU path is descriptor-driven and FUSED: one call covers a list of tile
-triples and becomes one kernel launch (csrc/gemm_tiles.hip). The CPU path loops
-over tiles with torch.linalg — it is the reference backend (the analog of the
+triples and becomes one kernel launch. ``ext.batch_gemm`` enters
+csrc/gemm_tiles.hip, which runs full-tile non-aliased batches on the glds
+kernels of csrc/gemm_tiles_v2.hip and edge shapes / in-place panel applies on
+its own guarded kernels; every batch runs on these in-tree kernels. The CPU
+path loops over tiles with torch.linalg — it is the reference backend (the analog of the
 reference's Backend::MC per-tile blaspp/lapackpp calls) and the
 oracle the GPU kernels are tested against.
 
@@ -19,7 +22,7 @@ import numpy as np
 import torch
 
 from ..types import Op, is_complex
-from ._ext import get_ext
+from ._ext import get_ext, has_ext
 
 _OP_CODE = {Op.NoTrans: 0, Op.Trans: 1, Op.ConjTrans: 2}
 
@@ -33,14 +36,9 @@ def _alpha_parts(alpha) -> Tuple[float, float]:
     return (c.real, c.imag)
 
 
-def make_descs(
-    c_offs: Sequence[int],
-    a_offs: Sequence[int],
-    b_offs: Sequence[int],
-    ktiles: int = 1,
-    a_kstride: int = 0,
-    b_kstride: int = 0,
-) -> np.ndarray:
+def make_descs(c_offs, a_offs, b_offs, ktiles=1, a_kstride=0, b_kstride=0) -> np.ndarray:
+    """[n, 6] int64 GemmDesc table (csrc/kernels.h). Offsets are per row;
+    ``ktiles`` and the K strides are scalars or per-row sequences."""
     n = len(c_offs)
     d = np.empty((n, 6), dtype=np.int64)
     d[:, 0] = np.asarray(c_offs, dtype=np.int64)
@@ -68,20 +66,12 @@ def gemm_fused(
     alpha,
     beta,
     inplace: bool = False,
-    uniform: bool = False,
 ) -> None:
     """GPU fused batched GEMM. ``descs``: np.ndarray [n,6] or device tensor.
 
     Set ``inplace=True`` when a desc's C block aliases its A block (panel
     applies) — it selects the kernel geometry that reads all of A before
     writing C.
-
-    ``uniform`` is accepted for API compatibility but no longer routes
-    anywhere: since round 2 the hand-written v2 glds kernel matches or beats
-    rocBLAS batched on the uniform nb=512 trailing shape (62.8 vs 62.5 TF
-    within one probe; round-1 v1 was 45 vs 65.7), so EVERY batch runs on the
-    in-tree CDNA4 kernels. rocBLAS remains available only as a test oracle
-    (``gemm_batched_lib``).
     """
     ext = get_ext()
     if isinstance(descs, np.ndarray):
@@ -133,8 +123,9 @@ def gemm_batched_lib(dt_ref: torch.Tensor, ptrC: torch.Tensor, ptrA: torch.Tenso
     """rocBLAS batched GEMM over precomputed device pointer arrays.
 
     Uniform-shape batches only (one K-product per C tile, no aliasing among
-    C entries). ~30% faster than the fused kernel on plain nb=512 f64 tiles
-    (57.8 vs 44.1 TF); mixed-ktiles phases keep ``gemm_fused``.
+    C entries). No algorithm routes here: the glds fused kernel matches it on
+    the uniform nb=512 f64 trailing shape (62.8 vs 62.5 TF in one probe). It
+    stays as the comparison point of ``tools/microbench.py``.
     """
     ar, ai = _alpha_parts(alpha)
     br, bi = _alpha_parts(beta)
@@ -162,9 +153,10 @@ def gemm_tile(C: torch.Tensor, A: torch.Tensor, B: torch.Tensor, opA: Op, opB: O
 # ---------------- factorization tile ops ----------------
 
 def potrf_bsz(dtype: torch.dtype) -> int:
-    # 64 for every dtype: the fused factor+invert kernel then fits next to
-    # trailing-GEMM blocks on a CU (LDS budget), so lookahead can overlap it.
-    return 64
+    """Diagonal-block size of the tile Cholesky: the extension's
+    ``kPotrfBsz`` (csrc/kernels.h), the same for every dtype. CPU-only
+    installs without the extension use the same 64."""
+    return get_ext().POTRF_BSZ if has_ext() else 64
 
 
 def dinv_workspace(nb: int, dtype: torch.dtype, device) -> torch.Tensor:
@@ -248,22 +240,18 @@ def gemm_items(
     alpha,
     beta,
     inplace: bool = False,
-    uniform: bool = False,
 ) -> None:
     """Tile-triple GEMM over element offsets into flat bases, CPU or GPU.
 
-    ``items``: sequence of (c_off, a_off, b_off). GPU: ONE fused kernel launch
-    (``uniform=True`` additionally allows the rocBLAS batched route — caller
-    guarantees unique C offsets). CPU: loop over reshaped nb x nb views (the
-    reference MC backend analog).
+    ``items``: sequence of (c_off, a_off, b_off). GPU: ONE fused kernel launch.
+    CPU: loop over reshaped nb x nb views (the reference MC backend analog).
     """
     if not len(items):
         return
     if C_base.is_cuda:
         c, a, b = zip(*items)
         gemm_fused(C_base, A_base, B_base, make_descs(c, a, b),
-                   nb, nb, nb, nb, nb, nb, opA, opB, alpha, beta, inplace=inplace,
-                   uniform=uniform)
+                   nb, nb, nb, nb, nb, nb, opA, opB, alpha, beta, inplace=inplace)
         return
     ts = nb * nb
     cv, av, bv = C_base.reshape(-1), A_base.reshape(-1), B_base.reshape(-1)

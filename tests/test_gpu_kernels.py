@@ -296,3 +296,112 @@ def test_bt_apply_group_tail_split():
     err = (outs["0"] - outs["1"]).abs().max().item()
     scale = outs["0"].abs().max().item() + 1
     assert err < 1e-11 * scale * n, err
+
+
+# ---- every fused-GEMM instantiation is launched at kernel level ----
+
+_REAL_OPS = [Op.NoTrans, Op.Trans]
+_ALL_OPS = [Op.NoTrans, Op.Trans, Op.ConjTrans]
+
+
+def _hp(dtype):
+    return torch.complex128 if dtype.is_complex else torch.float64
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("opA", _REAL_OPS)
+@pytest.mark.parametrize("opB", _REAL_OPS)
+def test_gemm_v2_bn64(dtype, opA, opB):
+    """glds kernel at BN=64 (N % 128 != 0): two descs, each accumulating two
+    K tiles, C -= A B."""
+    torch.manual_seed(6)
+    M, N, K = 128, 64, 16
+    a_shape = (M, K) if opA is Op.NoTrans else (K, M)
+    b_shape = (K, N) if opB is Op.NoTrans else (N, K)
+    A = _rand((4,) + a_shape, dtype)
+    B = _rand((4,) + b_shape, dtype)
+    C = _rand((2, M, N), dtype)
+    C0 = C.clone()
+    descs = ops.make_descs([0, M * N], [0, 2 * M * K], [0, 2 * K * N], ktiles=2,
+                           a_kstride=M * K, b_kstride=K * N)
+    ops.gemm_fused(C, A, B, descs, M, N, K, a_shape[1], b_shape[1], N, opA, opB, -1.0, 1.0)
+    torch.cuda.synchronize()
+    hp = _hp(dtype)
+    for d in range(2):
+        ref = C0[d].cpu().to(hp)
+        for t in (2 * d, 2 * d + 1):
+            ref = ref - _ref_op(A[t].cpu().to(hp), opA) @ _ref_op(B[t].cpu().to(hp), opB)
+        err = (C[d].cpu().to(hp) - ref).abs().max().item()
+        scale = ref.abs().max().item() + 1
+        assert err <= _tol(dtype, 2 * K) * scale, f"desc {d}: err={err}"
+
+
+@pytest.mark.parametrize("dtype,opA,opB",
+                         [(dt, a, b) for dt in (torch.float64, torch.float32)
+                          for a in _REAL_OPS for b in _REAL_OPS] +
+                         [(dt, a, b) for dt in (torch.complex128, torch.complex64)
+                          for a in _ALL_OPS for b in _ALL_OPS])
+def test_gemm_edge_shape_ops(dtype, opA, opB):
+    """Guarded register-staged kernels on a shape with no full block in any
+    dimension, every op pair."""
+    torch.manual_seed(7)
+    M, N, K = 33, 17, 5
+    a_shape = (M, K) if opA is Op.NoTrans else (K, M)
+    b_shape = (K, N) if opB is Op.NoTrans else (N, K)
+    A = _rand(a_shape, dtype)
+    B = _rand(b_shape, dtype)
+    C = _rand((M, N), dtype)
+    C0 = C.clone()
+    alpha, beta = (1.5 - 0.5j, 0.25 + 1j) if dtype.is_complex else (1.5, 0.25)
+    ops.gemm_fused(C, A, B, ops.make_descs([0], [0], [0]), M, N, K,
+                   a_shape[1], b_shape[1], N, opA, opB, alpha, beta)
+    torch.cuda.synchronize()
+    hp = _hp(dtype)
+    ref = alpha * (_ref_op(A.cpu().to(hp), opA) @ _ref_op(B.cpu().to(hp), opB)) \
+        + beta * C0.cpu().to(hp)
+    err = (C.cpu().to(hp) - ref).abs().max().item()
+    scale = ref.abs().max().item() + 1
+    assert err <= _tol(dtype, K) * scale, f"err={err} scale={scale}"
+
+
+def _check_inplace(dtype, nd, M, N, opA=Op.NoTrans, opB=Op.Trans):
+    """X[d] (M x N) = op(X[d]) @ op(B) in place for nd descs, K == N (and
+    M == N when opA transposes). One workgroup covers each X[d]."""
+    K = N
+    assert opA is Op.NoTrans or M == N
+    X = _rand((nd, M, N), dtype)
+    Bm = _rand((N, N), dtype)
+    X0 = X.clone()
+    offs = [i * M * N for i in range(nd)]
+    ops.gemm_fused(X, X, Bm, ops.make_descs(offs, offs, [0] * nd), M, N, K,
+                   N, N, N, opA, opB, 1.0, 0.0, inplace=True)
+    torch.cuda.synchronize()
+    hp = _hp(dtype)
+    for i in range(nd):
+        ref = _ref_op(X0[i].cpu().to(hp), opA) @ _ref_op(Bm.cpu().to(hp), opB)
+        err = (X[i].cpu().to(hp) - ref).abs().max().item()
+        assert err <= _tol(dtype, K) * (ref.abs().max().item() + 1), f"{i}: {err}"
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_gemm_inplace_full_block(dtype):
+    """In-place apply on full 128x128 blocks: the guard-free BN=128 kernel."""
+    torch.manual_seed(8)
+    _check_inplace(dtype, 3, 128, 128)
+
+
+def test_gemm_inplace_ragged_rows():
+    """In-place apply with an edge row block (the POTRF panel-apply shape):
+    the guarded BN=128 kernel."""
+    torch.manual_seed(9)
+    _check_inplace(torch.float64, 1, 100, 64)
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("n", [128, 100])
+@pytest.mark.parametrize("opA", _REAL_OPS)
+@pytest.mark.parametrize("opB", _REAL_OPS)
+def test_gemm_inplace_op_pairs(dtype, n, opA, opB):
+    """Both BN=128 kernels (n=128 guard-free, n=100 guarded), every op pair."""
+    torch.manual_seed(10)
+    _check_inplace(dtype, 2, n, n, opA, opB)
