@@ -129,6 +129,37 @@ int run_geig(int ctx, char uplo, void* a, const struct DLAF_descriptor& da,
   }
 }
 
+int run_eigvals(int ctx, char uplo, void* a, const struct DLAF_descriptor& da,
+                void* w, const char* adt, const char* wdt) {
+  Gil g;
+  try {
+    auto arr = np_view(ctx, a, da, adt);
+    auto wv = np_vec(w, da.n, wdt);
+    return capi_->attr("dlaf_hermitian_eigenvalues")(
+        ctx, std::string(1, uplo), arr, desc_obj(da), wv).cast<int>();
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: eigenvalues failed: %s\n", e.what());
+    return -1;
+  }
+}
+
+int run_geigvals(int ctx, char uplo, void* a, const struct DLAF_descriptor& da,
+                 void* b, const struct DLAF_descriptor& db, void* w,
+                 const char* adt, const char* wdt) {
+  Gil g;
+  try {
+    auto av = np_view(ctx, a, da, adt);
+    auto bv = np_view(ctx, b, db, adt);
+    auto wv = np_vec(w, da.n, wdt);
+    return capi_->attr("dlaf_hermitian_generalized_eigenvalues")(
+        ctx, std::string(1, uplo), av, desc_obj(da), bv, desc_obj(db), wv)
+        .cast<int>();
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: gen eigenvalues failed: %s\n", e.what());
+    return -1;
+  }
+}
+
 struct DLAF_descriptor from_sl(int n, const int d[9], int m = -1) {
   struct DLAF_descriptor out;
   out.m = m >= 0 ? m : d[2];
@@ -283,7 +314,26 @@ int dlaf_hermitian_generalized_eigensolver_factorized_z(
                   true);
 }
 
-#define SL_POTRF(name, suf, ctype)                                             \
+int dlaf_symmetric_eigenvalues_d(int ctx, char uplo, double* a,
+                                 struct DLAF_descriptor da, double* w) {
+  return run_eigvals(ctx, uplo, a, da, w, "float64", "float64");
+}
+int dlaf_hermitian_eigenvalues_z(int ctx, char uplo, dlaf_complex_z* a,
+                                 struct DLAF_descriptor da, double* w) {
+  return run_eigvals(ctx, uplo, a, da, w, "complex128", "float64");
+}
+int dlaf_symmetric_generalized_eigenvalues_d(
+    int ctx, char uplo, double* a, struct DLAF_descriptor da, double* b,
+    struct DLAF_descriptor db, double* w) {
+  return run_geigvals(ctx, uplo, a, da, b, db, w, "float64", "float64");
+}
+int dlaf_hermitian_generalized_eigenvalues_z(
+    int ctx, char uplo, dlaf_complex_z* a, struct DLAF_descriptor da,
+    dlaf_complex_z* b, struct DLAF_descriptor db, double* w) {
+  return run_geigvals(ctx, uplo, a, da, b, db, w, "complex128", "float64");
+}
+
+#define SL_POTRF(name, suf, ctype)                                            \
   void name(char uplo, int n, ctype* a, int ia, int ja, const int desca[9],    \
             int* info) {                                                       \
     (void)ia;                                                                  \

@@ -14,10 +14,17 @@
 #include <c10/cuda/CUDACachingAllocator.h>
 #include <hip/hip_runtime.h>
 
+#include <ATen/Parallel.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <thread>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 
 #include "kernels.h"
+#include "sturm.h"
 
 // csrc/rocblas_batch.cpp
 void lib_gemm_batched(torch::Tensor dt, torch::Tensor ptrC, torch::Tensor ptrA,
@@ -215,6 +222,119 @@ void secular_roots(torch::Tensor d, torch::Tensor z2, double rho,
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- tridiagonal eigenvalues by Sturm bisection (sturm.h / bisect.hip) ----
+
+void check_tridiag(const torch::Tensor& d, const torch::Tensor& e2) {
+  TORCH_CHECK(d.scalar_type() == torch::kFloat64 &&
+              e2.scalar_type() == torch::kFloat64, "float64 required");
+  TORCH_CHECK(d.dim() == 1 && e2.dim() == 1 && d.is_contiguous() &&
+              e2.is_contiguous(), "contiguous 1-D tensors required");
+  TORCH_CHECK(d.size(0) < (int64_t(1) << 30), "n too large");
+  TORCH_CHECK(e2.size(0) == std::max<int64_t>(d.size(0) - 1, 0),
+              "e2 must have n-1 entries");
+  TORCH_CHECK(e2.device() == d.device(), "d and e2 on different devices");
+}
+
+// at::parallel_for is serial in a translation unit built without OpenMP;
+// plain threads over contiguous index ranges do the job (as band_chase.cpp).
+template <typename F>
+void host_parallel(int64_t begin, int64_t end, int64_t work_per_item, F&& f) {
+  const int64_t m = end - begin;
+  int64_t nt = std::min<int64_t>(at::get_num_threads(), m);
+  if (m * work_per_item < (int64_t(1) << 16)) nt = 1;  // not worth a thread
+  if (nt <= 1) {
+    if (m > 0) f(begin, end);
+    return;
+  }
+  std::vector<std::thread> pool;
+  for (int64_t t = 0; t < nt; ++t)
+    pool.emplace_back([&f, begin, m, nt, t] {
+      f(begin + m * t / nt, begin + m * (t + 1) / nt);
+    });
+  for (auto& th : pool) th.join();
+}
+
+// Host twins of the kernels: the same sturm.h functions in a plain loop.
+void tridiag_bisect_host(const double* d, const double* e2, int n, int k_begin,
+                         int k_end, double gl, double gu, double pivmin,
+                         double* w) {
+  if (n <= 0 || k_begin >= k_end) return;
+  host_parallel(k_begin, k_end, 64 * (int64_t)n, [&](int64_t b, int64_t e) {
+    for (int64_t k = b; k < e; ++k) {
+      dlaf::sturm::Bisect s;
+      dlaf::sturm::bisect_begin(s, gl, gu, pivmin);
+      while (!s.done)
+        dlaf::sturm::bisect_update(
+            s, dlaf::sturm::count(d, e2, n, pivmin, s.mid), (int)k, pivmin);
+      w[k - k_begin] = s.mid;
+    }
+  });
+}
+
+void sturm_count_host(const double* d, const double* e2, int n, double pivmin,
+                      const double* x, int nx, long long* count) {
+  host_parallel(0, nx, n, [&](int64_t b, int64_t e) {
+    for (int64_t j = b; j < e; ++j)
+      count[j] = n > 0 ? dlaf::sturm::count(d, e2, n, pivmin, x[j]) : 0;
+  });
+}
+
+// (gl, gu, pivmin) of sturm::interval for CPU float64 d [n], e [n-1].
+std::tuple<double, double, double> sturm_interval(torch::Tensor d,
+                                                  torch::Tensor e) {
+  check_tridiag(d, e);
+  TORCH_CHECK(!d.is_cuda(), "sturm_interval runs on the host");
+  double gl = 0, gu = 0, pivmin = DBL_MIN;
+  if (d.size(0) > 0)
+    dlaf::sturm::interval(d.data_ptr<double>(), e.data_ptr<double>(),
+                          (int)d.size(0), &gl, &gu, &pivmin);
+  return {gl, gu, pivmin};
+}
+
+// w[k - k_begin] = eigenvalue k of tridiag(d, e), k in [k_begin, k_end).
+void tridiag_bisect(torch::Tensor d, torch::Tensor e2, int64_t k_begin,
+                    int64_t k_end, double gl, double gu, double pivmin,
+                    torch::Tensor w) {
+  check_tridiag(d, e2);
+  const int64_t n = d.size(0);
+  TORCH_CHECK(0 <= k_begin && k_begin <= k_end && k_end <= n,
+              "bad eigenvalue index range");
+  TORCH_CHECK(w.scalar_type() == torch::kFloat64 && w.is_contiguous() &&
+              w.numel() >= k_end - k_begin && w.device() == d.device(),
+              "bad output tensor");
+  if (d.is_cuda()) {
+    dlaf::tridiag_bisect(d.data_ptr<double>(), e2.data_ptr<double>(), (int)n,
+                         (int)k_begin, (int)k_end, gl, gu, pivmin,
+                         w.data_ptr<double>(), cur_stream());
+    HIP_CHECK(hipGetLastError());
+  } else {
+    tridiag_bisect_host(d.data_ptr<double>(), e2.data_ptr<double>(), (int)n,
+                        (int)k_begin, (int)k_end, gl, gu, pivmin,
+                        w.data_ptr<double>());
+  }
+}
+
+// count[j] = number of eigenvalues of tridiag(d, e) strictly below x[j].
+void sturm_count(torch::Tensor d, torch::Tensor e2, double pivmin,
+                 torch::Tensor x, torch::Tensor count) {
+  check_tridiag(d, e2);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat64 && x.dim() == 1 &&
+              x.is_contiguous() && x.device() == d.device(), "bad x");
+  TORCH_CHECK(count.scalar_type() == at::kLong && count.is_contiguous() &&
+              count.numel() >= x.numel() && count.device() == d.device(),
+              "bad count tensor");
+  const int n = (int)d.size(0), nx = (int)x.size(0);
+  auto cp = (long long*)count.data_ptr<int64_t>();
+  if (d.is_cuda()) {
+    dlaf::sturm_count(d.data_ptr<double>(), e2.data_ptr<double>(), n, pivmin,
+                      x.data_ptr<double>(), nx, cp, cur_stream());
+    HIP_CHECK(hipGetLastError());
+  } else {
+    sturm_count_host(d.data_ptr<double>(), e2.data_ptr<double>(), n, pivmin,
+                     x.data_ptr<double>(), nx, cp);
+  }
+}
+
 bool bt_apply_group(torch::Tensor E, torch::Tensor V, torch::Tensor VTt,
                     int64_t base0, int64_t b, int64_t G, int64_t R,
                     int64_t nwin) {
@@ -263,6 +383,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("panel_qr", &panel_qr, "cooperative whole-panel QR (one launch)");
   m.def("secular_roots", &secular_roots,
         "D&C secular-equation roots, one thread per root");
+  m.def("tridiag_bisect", &tridiag_bisect,
+        "tridiagonal eigenvalues [k_begin, k_end) by Sturm bisection, one "
+        "thread per eigenvalue (host loop for CPU tensors)");
+  m.def("sturm_count", &sturm_count,
+        "number of tridiagonal eigenvalues strictly below each x");
+  m.def("sturm_interval", &sturm_interval,
+        "(gl, gu, pivmin): widened Gershgorin interval and pivot floor");
   m.def("dc_deflate_scan", &dc_deflate_scan,
         "sequential deflation scan for the D&C merge");
   m.def("band_chase", &band_chase,

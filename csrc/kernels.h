@@ -115,4 +115,16 @@ int panel_qr(S* P, long m, int nb, long ldp, S* taus,
 void secular_roots(const double* d, const double* z2, int k, double rho,
                    long long* sidx, double* mu, hipStream_t stream);
 
+// ---- tridiagonal eigenvalues by Sturm bisection, csrc/bisect.hip ----
+// e2[i] = e[i]^2 (n-1 entries); gl/gu/pivmin as sturm::interval computes them.
+// w[k - k_begin] = eigenvalue k (ascending) for k in [k_begin, k_end);
+// count[j] = number of eigenvalues strictly below x[j]. n <= 0 or an empty
+// range launches nothing. d/e2 are staged through LDS kBisectChunk at a time.
+constexpr int kBisectChunk = 1024;
+void tridiag_bisect(const double* d, const double* e2, int n, int k_begin,
+                    int k_end, double gl, double gu, double pivmin, double* w,
+                    hipStream_t stream);
+void sturm_count(const double* d, const double* e2, int n, double pivmin,
+                 const double* x, int nx, long long* count, hipStream_t stream);
+
 }  // namespace dlaf

@@ -18,7 +18,9 @@ Public API (mirrors the reference's free-function API):
     triangular_inverse, generalized_to_standard, reduction_to_band,
     band_to_tridiagonal, tridiagonal_eigensolver, bt_band_to_tridiagonal,
     bt_reduction_to_band, hermitian_eigensolver, hermitian_generalized_eigensolver,
-    max_norm
+    max_norm, and the eigenvalues-only drivers tridiagonal_eigenvalues,
+    tridiagonal_eigenvalue_count, hermitian_eigenvalues,
+    hermitian_generalized_eigenvalues
 """
 
 from .types import Side, UpLo, Op, Diag  # noqa: F401
@@ -47,6 +49,12 @@ from .algs.band2tridiag import (  # noqa: F401
     bt_band_to_tridiagonal,
 )
 from .algs.tridiag_dc import tridiagonal_eigensolver  # noqa: F401
+from .algs.tridiag_bisect import (  # noqa: F401
+    tridiagonal_eigenvalues,
+    tridiagonal_eigenvalue_count,
+    hermitian_eigenvalues,
+    hermitian_generalized_eigenvalues,
+)
 from .algs.permutations import permute_columns, permute_rows  # noqa: F401
 from .algs.redistribute import redistribute  # noqa: F401
 from .matrix.mirror import MatrixMirror, MatrixRef, save_matrix, load_matrix  # noqa: F401

@@ -29,6 +29,8 @@ from .matrix.matrix import Matrix
 from .algs.cholesky import cholesky_factorization
 from .algs.inverse import inverse_from_cholesky_factor, triangular_inverse
 from .algs.eigensolver import hermitian_eigensolver, hermitian_generalized_eigensolver
+from .algs.tridiag_bisect import (hermitian_eigenvalues,
+                                  hermitian_generalized_eigenvalues)
 
 
 @dataclass
@@ -253,6 +255,59 @@ def dlaf_hermitian_generalized_eigensolver(ctx: int, uplo: str, a_local,
     if isinstance(w_out, np.ndarray):
         w_out[: w.shape[0]] = wt[: w.shape[0]].numpy()
     _unwrap_local(evecs, z_local)
+    _unwrap_local(mat_b, b_local)
+    return 0
+
+
+def _store_w(w: torch.Tensor, w_out) -> None:
+    wt = torch.as_tensor(w_out)
+    wt[: w.shape[0]] = w.cpu().to(wt.dtype)
+    if isinstance(w_out, np.ndarray):
+        w_out[: w.shape[0]] = wt[: w.shape[0]].numpy()
+
+
+def dlaf_hermitian_eigenvalues(ctx: int, uplo: str, a_local,
+                               desc: DLAF_descriptor, w_out, il: int = 0,
+                               iu: Optional[int] = None) -> int:
+    """Eigenvalues only (``jobz='N'``) of the Hermitian matrix in ``a_local``.
+
+    w_out: [n] real output buffer; eigenvalues ``il <= k < iu`` (0-based,
+    ascending) land in ``w_out[:iu-il]``. ``a_local`` is overwritten as by
+    ``dlaf_hermitian_eigensolver``.
+    """
+    grid = _grid(ctx)
+    dev = _device_for(grid)
+    mat = _wrap_local(a_local, desc, grid, dev)
+    if uplo.upper() == "U":
+        from .algs._uplo import transpose_storage
+        transpose_storage(mat)
+    w = hermitian_eigenvalues(UpLo.Lower, mat,
+                              grid if grid.distributed else None,
+                              eigenvalues_index_begin=il,
+                              eigenvalues_index_end=iu)
+    _store_w(w, w_out)
+    _unwrap_local(mat, a_local)
+    return 0
+
+
+def dlaf_hermitian_generalized_eigenvalues(ctx: int, uplo: str, a_local,
+                                           desca: DLAF_descriptor, b_local,
+                                           descb: DLAF_descriptor, w_out,
+                                           factorized: bool = False) -> int:
+    """Eigenvalues only of A x = lambda B x; ``b_local`` is overwritten with
+    its Cholesky factor as by ``dlaf_hermitian_generalized_eigensolver``."""
+    grid = _grid(ctx)
+    dev = _device_for(grid)
+    mat_a = _wrap_local(a_local, desca, grid, dev)
+    mat_b = _wrap_local(b_local, descb, grid, dev)
+    if uplo.upper() == "U":
+        from .algs._uplo import transpose_storage
+        transpose_storage(mat_a)
+        transpose_storage(mat_b)
+    w = hermitian_generalized_eigenvalues(
+        UpLo.Lower, mat_a, mat_b, grid if grid.distributed else None,
+        factorized=factorized)
+    _store_w(w, w_out)
     _unwrap_local(mat_b, b_local)
     return 0
 

@@ -95,6 +95,20 @@ int dlaf_hermitian_generalized_eigensolver_factorized_z(
     dlaf_complex_z* b, struct DLAF_descriptor descb,
     double* w, dlaf_complex_z* z, struct DLAF_descriptor descz);
 
+/* eigenvalues only (ScaLAPACK jobz='N'): all n eigenvalues into w, ascending,
+ * by Sturm bisection on the tridiagonal; no eigenvectors are formed. a (and
+ * b, as in the eigensolver variants) is overwritten. */
+int dlaf_symmetric_eigenvalues_d(int ctx, char uplo, double* a,
+                                 struct DLAF_descriptor desca, double* w);
+int dlaf_hermitian_eigenvalues_z(int ctx, char uplo, dlaf_complex_z* a,
+                                 struct DLAF_descriptor desca, double* w);
+int dlaf_symmetric_generalized_eigenvalues_d(
+    int ctx, char uplo, double* a, struct DLAF_descriptor desca,
+    double* b, struct DLAF_descriptor descb, double* w);
+int dlaf_hermitian_generalized_eigenvalues_z(
+    int ctx, char uplo, dlaf_complex_z* a, struct DLAF_descriptor desca,
+    dlaf_complex_z* b, struct DLAF_descriptor descb, double* w);
+
 /* ScaLAPACK-style shims (dlaf_pdpotrf etc.): desca is the 9-int ScaLAPACK
  * descriptor (DTYPE_, CTXT_, M_, N_, MB_, NB_, RSRC_, CSRC_, LLD_). */
 void dlaf_pdpotrf(char uplo, int n, double* a, int ia, int ja, const int desca[9], int* info);

@@ -25,6 +25,7 @@ setup(
                 "csrc/factor.hip",
                 "csrc/panel_qr.hip",
                 "csrc/secular.hip",
+                "csrc/bisect.hip",
                 "csrc/rocblas_batch.cpp",
                 "csrc/chase_gpu.hip",
             ],

@@ -1,6 +1,12 @@
-"""Timing breakdown of the eigensolver pipeline on GPU (SYEV config 4 shape)."""
+"""Timing breakdown of the eigensolver pipeline on GPU (SYEV config 4 shape).
+
+usage: time_eigensolver.py [n [nb [band [d|z|s|c]]]] [--eigenvalues-only]
+``--eigenvalues-only`` times the values-only pipeline instead: red2band,
+band2tridiag, Sturm bisection (no D&C, no back-transforms)."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+values_only = "--eigenvalues-only" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--eigenvalues-only"]
 import torch
 from dlaf_amd import Matrix, UpLo
 from dlaf_amd.matrix import util as mutil
@@ -30,6 +36,17 @@ def sync():
 stamps = [("start", time.perf_counter())]
 refl = reduction_to_band(mat, band); sync(); stamps.append(("red2band", time.perf_counter()))
 tri = band_to_tridiagonal(UpLo.Lower, band, mat); sync(); stamps.append(("band2tridiag", time.perf_counter()))
+if values_only:
+    from dlaf_amd import tridiagonal_eigenvalues
+    w = tridiagonal_eigenvalues(tri.d, tri.e, device=mat.device); sync(); stamps.append(("tridiag_bisect", time.perf_counter()))
+    tot = stamps[-1][1] - stamps[0][1]
+    print(f"HEEV-values[{mat.dtype}] n={n} nb={nb} band={band} dev={dev}: total {tot:.2f}s")
+    for (nm, t1), (_, t0) in zip(stamps[1:], stamps[:-1]):
+        print(f"  {nm:16s} {t1-t0:8.3f}s")
+    if a0 is not None:
+        werr = (w - torch.linalg.eigvalsh(a0).to(w.dtype)).abs().max().item()
+        print(f"  werr={werr:.2e}")
+    sys.exit(0)
 w, E_real = tridiagonal_eigensolver(tri.d, tri.e, device=mat.device); sync(); stamps.append(("tridiag_dc", time.perf_counter()))
 E = E_real.to(mat.dtype).contiguous()
 if tri.phases is not None:
