@@ -25,6 +25,7 @@
 
 #include "kernels.h"
 #include "sturm.h"
+#include "tridiag_lu.h"
 
 // csrc/rocblas_batch.cpp
 void lib_gemm_batched(torch::Tensor dt, torch::Tensor ptrC, torch::Tensor ptrA,
@@ -335,6 +336,100 @@ void sturm_count(torch::Tensor d, torch::Tensor e2, double pivmin,
   }
 }
 
+// ---- shifted tridiagonal solves (tridiag_lu.h / invit.hip) ----
+
+// Host twin of the kernel: the same tridiag_lu.h functions, columns in
+// blocks of 64 with the row loop outside so X and U are walked row by row.
+void tridiag_shifted_solve_host(const double* d, const double* e, int n,
+                                const double* lam, int k, double tol,
+                                double* X, int64_t ldx, double* U,
+                                int64_t cols) {
+  if (n <= 0 || k <= 0) return;
+  constexpr int kBlock = 64;
+  const int64_t nblk = (k + kBlock - 1) / kBlock;
+  const int64_t plane = (int64_t)n * cols;
+  host_parallel(0, nblk, 64 * (int64_t)n, [&](int64_t bb, int64_t be) {
+    for (int64_t blk = bb; blk < be; ++blk) {
+      const int64_t c0 = blk * kBlock;
+      const int w = (int)std::min<int64_t>(kBlock, k - c0);
+      double a[kBlock], b[kBlock], xcur[kBlock], y1[kBlock], y2[kBlock];
+      for (int j = 0; j < w; ++j) {
+        a[j] = d[0] - lam[c0 + j];
+        b[j] = n > 1 ? e[0] : 0.0;
+        xcur[j] = X[c0 + j];
+        y1[j] = y2[j] = 0.0;
+      }
+      for (int64_t i = 0; i < n; ++i) {
+        const double sub = i < n - 1 ? e[i] : 0.0;
+        const double dn = i + 1 < n ? d[i + 1] : 0.0;
+        const double ne = i + 1 < n - 1 ? e[i + 1] : 0.0;
+        double* xr = X + i * ldx + c0;
+        double* ur = U + i * cols + c0;
+        for (int j = 0; j < w; ++j) {
+          double u0, u1, u2, xi = xcur[j];
+          double xj = i + 1 < n ? xr[ldx + j] : 0.0;
+          dlaf::trilu::forward(a[j], b[j], sub, dn - lam[c0 + j], ne, tol, xi,
+                               xj, u0, u1, u2);
+          xcur[j] = xj;
+          xr[j] = xi;
+          ur[j] = u0;
+          ur[plane + j] = u1;
+          ur[2 * plane + j] = u2;
+        }
+      }
+      for (int64_t i = n - 1; i >= 0; --i) {
+        double* xr = X + i * ldx + c0;
+        const double* ur = U + i * cols + c0;
+        for (int j = 0; j < w; ++j) {
+          const double y = dlaf::trilu::back(xr[j], ur[j], ur[plane + j],
+                                             ur[2 * plane + j], y1[j], y2[j]);
+          y2[j] = y1[j];
+          y1[j] = y;
+          xr[j] = y;
+        }
+      }
+    }
+  });
+}
+
+// X[:, j] <- (T - lam[j] I)^-1 X[:, j] for tridiag(d, e); work [3, n, cols].
+void tridiag_shifted_solve(torch::Tensor d, torch::Tensor e, torch::Tensor lam,
+                           double tol, torch::Tensor X, torch::Tensor work) {
+  check_tridiag(d, e);
+  const int64_t n = d.size(0);
+  TORCH_CHECK(lam.scalar_type() == torch::kFloat64 && lam.dim() == 1 &&
+              lam.is_contiguous() && lam.device() == d.device(), "bad lam");
+  const int64_t k = lam.size(0);
+  TORCH_CHECK(k < (int64_t(1) << 30), "too many columns");
+  TORCH_CHECK(X.scalar_type() == torch::kFloat64 && X.dim() == 2 &&
+              X.size(0) == n && X.size(1) == k && X.device() == d.device(),
+              "X must be float64 [n, k] on d's device");
+  // a column slice of a wider row-major matrix is fine: rows ldx apart
+  TORCH_CHECK(k == 0 || n == 0 ||
+              (X.stride(1) == 1 && (n == 1 || X.stride(0) >= k)),
+              "X must be row-major with unit column stride");
+  TORCH_CHECK(work.scalar_type() == torch::kFloat64 && work.dim() == 3 &&
+              work.is_contiguous() && work.size(0) == 3 &&
+              work.size(1) == n && work.size(2) >= k &&
+              work.device() == d.device(),
+              "work must be contiguous float64 [3, n, >= k]");
+  TORCH_CHECK(tol > 0.0, "tol must be positive");
+  if (n == 0 || k == 0) return;
+  const int64_t ldx = X.stride(0), cols = work.size(2);
+  if (d.is_cuda()) {
+    dlaf::tridiag_shifted_solve(d.data_ptr<double>(), e.data_ptr<double>(),
+                                (int)n, lam.data_ptr<double>(), (int)k, tol,
+                                X.data_ptr<double>(), ldx,
+                                work.data_ptr<double>(), cols, cur_stream());
+    HIP_CHECK(hipGetLastError());
+  } else {
+    tridiag_shifted_solve_host(d.data_ptr<double>(), e.data_ptr<double>(),
+                               (int)n, lam.data_ptr<double>(), (int)k, tol,
+                               X.data_ptr<double>(), ldx,
+                               work.data_ptr<double>(), cols);
+  }
+}
+
 bool bt_apply_group(torch::Tensor E, torch::Tensor V, torch::Tensor VTt,
                     int64_t base0, int64_t b, int64_t G, int64_t R,
                     int64_t nwin) {
@@ -388,6 +483,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "thread per eigenvalue (host loop for CPU tensors)");
   m.def("sturm_count", &sturm_count,
         "number of tridiagonal eigenvalues strictly below each x");
+  m.def("tridiag_shifted_solve", &tridiag_shifted_solve,
+        "in-place (T - lam[j] I) y_j = x_j by pivoted LU, one thread per "
+        "column (host loop for CPU tensors)",
+        py::arg("d"), py::arg("e"), py::arg("lam"), py::arg("tol"),
+        py::arg("X"), py::arg("work"));
   m.def("sturm_interval", &sturm_interval,
         "(gl, gu, pivmin): widened Gershgorin interval and pivot floor");
   m.def("dc_deflate_scan", &dc_deflate_scan,

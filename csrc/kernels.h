@@ -127,4 +127,14 @@ void tridiag_bisect(const double* d, const double* e2, int n, int k_begin,
 void sturm_count(const double* d, const double* e2, int n, double pivmin,
                  const double* x, int nx, long long* count, hipStream_t stream);
 
+// ---- shifted tridiagonal solves for inverse iteration, csrc/invit.hip ----
+// (T - lam[j] I) y_j = x_j for columns j < k, in place on X (row i of column
+// j at X[i*ldx + j]), by the pivoted LU of tridiag_lu.h with pivot floor tol.
+// e has n-1 entries (not squared). work holds the U rows as [3, n, cols],
+// cols >= k. n <= 0 or k <= 0 launches nothing.
+void tridiag_shifted_solve(const double* d, const double* e, int n,
+                           const double* lam, int k, double tol, double* X,
+                           long long ldx, double* work, long long cols,
+                           hipStream_t stream);
+
 }  // namespace dlaf

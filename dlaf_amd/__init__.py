@@ -20,7 +20,8 @@ Public API (mirrors the reference's free-function API):
     bt_reduction_to_band, hermitian_eigensolver, hermitian_generalized_eigensolver,
     max_norm, and the eigenvalues-only drivers tridiagonal_eigenvalues,
     tridiagonal_eigenvalue_count, hermitian_eigenvalues,
-    hermitian_generalized_eigenvalues
+    hermitian_generalized_eigenvalues, and the partial-spectrum eigenvector
+    solvers tridiagonal_eigenvectors, tridiagonal_eigensolver_bisect
 """
 
 from .types import Side, UpLo, Op, Diag  # noqa: F401
@@ -54,6 +55,10 @@ from .algs.tridiag_bisect import (  # noqa: F401
     tridiagonal_eigenvalue_count,
     hermitian_eigenvalues,
     hermitian_generalized_eigenvalues,
+)
+from .algs.tridiag_invit import (  # noqa: F401
+    tridiagonal_eigenvectors,
+    tridiagonal_eigensolver_bisect,
 )
 from .algs.permutations import permute_columns, permute_rows  # noqa: F401
 from .algs.redistribute import redistribute  # noqa: F401

@@ -18,6 +18,8 @@ from ..comm.grid import CommGrid
 from .red2band import reduction_to_band, bt_reduction_to_band
 from .band2tridiag import band_to_tridiagonal, bt_band_to_tridiagonal
 from .tridiag_dc import tridiagonal_eigensolver
+from .tridiag_bisect import _real_dtype, _resolve_value_range, _setup
+from .tridiag_invit import tridiagonal_eigensolver_bisect
 from .cholesky import cholesky_factorization
 from .gen_to_std import generalized_to_standard
 from .triangular import triangular_solver
@@ -47,6 +49,8 @@ def hermitian_eigensolver(
     band: Optional[int] = None,
     eigenvalues_index_begin: int = 0,
     eigenvalues_index_end: Optional[int] = None,
+    tridiag_solver: str = "dc",
+    eigenvalues_value_range: Optional[Tuple[float, float]] = None,
 ) -> Tuple[torch.Tensor, Matrix]:
     """Eigendecomposition A = E diag(w) E^H of a Hermitian tiled matrix.
 
@@ -54,6 +58,16 @@ def hermitian_eigensolver(
     E [Matrix, same dtype/device/grid]); the partial-spectrum indices select
     eigenvector columns (back-transforms applied only to the slice, the
     reference's MatrixRef mechanism).
+
+    ``tridiag_solver`` picks the tridiagonal stage: ``"dc"`` (default) solves
+    the whole tridiagonal problem by divide and conquer and slices;
+    ``"bisect"`` computes only the selected eigenpairs by Sturm bisection and
+    inverse iteration in O(n*k) memory (local grids only), with eigenvalues
+    bitwise equal to ``hermitian_eigenvalues``.
+
+    ``eigenvalues_value_range=(vl, vu)`` selects the eigenvalues in the
+    HALF-OPEN interval ``[vl, vu)`` instead of an index range (the two are
+    mutually exclusive), as in ``hermitian_eigenvalues``.
     """
     from ..core.asserts import dlaf_assert
     dlaf_assert(uplo == UpLo.Lower,
@@ -62,6 +76,12 @@ def hermitian_eigensolver(
     dlaf_assert(d.m == d.n and d.mb == d.nb,
                 "square matrix with square tiles required", d.size,
                 d.tile_size)
+    dlaf_assert(tridiag_solver in ("dc", "bisect"),
+                "tridiag_solver must be 'dc' or 'bisect'", tridiag_solver)
+    dlaf_assert(eigenvalues_value_range is None
+                or (eigenvalues_index_begin == 0
+                    and eigenvalues_index_end is None),
+                "eigenvalues_value_range excludes an index range")
     n = d.m
     g = grid if grid is not None else mat.grid
     if band is None:
@@ -78,10 +98,17 @@ def hermitian_eigensolver(
         # tiny problem (at or below one tile/band): direct dense
         # eigendecomposition
         return _eigh_direct(mat, g, eigenvalues_index_begin,
-                            eigenvalues_index_end)
+                            eigenvalues_index_end, eigenvalues_value_range)
     if g is not None and g.distributed:
         import os
+        dlaf_assert(tridiag_solver == "dc",
+                    "tridiag_solver='bisect' is not implemented on a "
+                    "distributed grid (eigenvalue clusters cross the "
+                    "eigenvector stripes); use 'dc'")
         if os.environ.get("DLAF_DIST_EIG", "tiled") == "replicated":
+            dlaf_assert(eigenvalues_value_range is None,
+                        "eigenvalues_value_range needs the tiled "
+                        "distributed pipeline")
             # round-1 replicated-dense design, kept as a debug fallback
             from .eigensolver_dist import hermitian_eigensolver_dist
             return hermitian_eigensolver_dist(
@@ -92,15 +119,29 @@ def hermitian_eigensolver(
         return hermitian_eigensolver_tiled(
             uplo, mat, g, band,
             eigenvalues_index_begin=eigenvalues_index_begin,
-            eigenvalues_index_end=eigenvalues_index_end)
+            eigenvalues_index_end=eigenvalues_index_end,
+            eigenvalues_value_range=eigenvalues_value_range)
     ib = eigenvalues_index_begin
     ie = n if eigenvalues_index_end is None else eigenvalues_index_end
 
     refl = reduction_to_band(mat, band)
     tri = band_to_tridiagonal(UpLo.Lower, band, mat)
-    w, E_real = tridiagonal_eigensolver(tri.d, tri.e, device=mat.device)
-    w = w[ib:ie].clone()
-    E = E_real[:, ib:ie].to(mat.dtype).contiguous()
+    if eigenvalues_value_range is not None:
+        ib, ie = _value_range_indices(tri, eigenvalues_value_range,
+                                      mat.device)
+    if tridiag_solver == "bisect":
+        # only the selected eigenpairs: E_real is [n, ie - ib], never n x n
+        dlaf_assert(0 <= ib <= n and ie <= n, "eigenvalue index range out "
+                    "of bounds", ib, ie, n)
+        w, E_real = tridiagonal_eigensolver_bisect(
+            tri.d, tri.e, ib, max(ie, ib), device=mat.device)
+        w = w.to(_real_dtype(mat.dtype))
+        E = E_real.to(mat.dtype)
+        del E_real
+    else:
+        w, E_real = tridiagonal_eigensolver(tri.d, tri.e, device=mat.device)
+        w = w[ib:ie].clone()
+        E = E_real[:, ib:ie].to(mat.dtype).contiguous()
     bt_band_to_tridiagonal(E, tri)
     bt_reduction_to_band(E, mat, refl)
 
@@ -112,7 +153,15 @@ def hermitian_eigensolver(
     return w, evecs
 
 
-def _eigh_direct(mat: Matrix, g, ib: int, ie) -> Tuple[torch.Tensor, Matrix]:
+def _value_range_indices(tri, vrange, device) -> Tuple[int, int]:
+    """[vl, vu) -> index range, by Sturm counts on the tridiagonal (replicated
+    on a distributed grid, so every rank resolves the same range)."""
+    dh, e2h, _, _, pivmin = _setup(tri.d, tri.e)
+    return _resolve_value_range((dh, e2h, pivmin), vrange, device)
+
+
+def _eigh_direct(mat: Matrix, g, ib: int, ie,
+                 vrange=None) -> Tuple[torch.Tensor, Matrix]:
     """Dense fallback for problems at or below one band/tile: assemble the
     Hermitian matrix, torch.linalg.eigh (rank-replicated when distributed),
     slice the requested spectrum."""
@@ -122,6 +171,8 @@ def _eigh_direct(mat: Matrix, g, ib: int, ie) -> Tuple[torch.Tensor, Matrix]:
     a = mat.to_global()
     a = torch.tril(a) + torch.tril(a, -1).mH
     w_all, E_all = torch.linalg.eigh(a)
+    if vrange is not None:
+        ib, ie = _resolve_value_range(w_all, vrange, mat.device)
     w = w_all[ib:ie].clone()
     E = E_all[:, ib:ie].contiguous()
     nE = E.shape[1]
@@ -152,12 +203,15 @@ def hermitian_generalized_eigensolver(
     band: Optional[int] = None,
     eigenvalues_index_begin: int = 0,
     eigenvalues_index_end: Optional[int] = None,
+    tridiag_solver: str = "dc",
+    eigenvalues_value_range: Optional[Tuple[float, float]] = None,
 ) -> Tuple[torch.Tensor, Matrix]:
     """Generalized problem A x = lambda B x (B HPD): returns (w, E).
 
     ``mat_b`` is overwritten with its Cholesky factor (or is already the
     factor when ``factorized``); ``mat_a`` is overwritten. Reference:
-    ``eigensolver/gen_eigensolver/impl.h:30-104``.
+    ``eigensolver/gen_eigensolver/impl.h:30-104``. ``tridiag_solver`` and
+    ``eigenvalues_value_range`` as in ``hermitian_eigensolver``.
     """
     assert uplo == UpLo.Lower
     g = grid if grid is not None else mat_a.grid
@@ -168,6 +222,8 @@ def hermitian_generalized_eigensolver(
         UpLo.Lower, mat_a, g, band=band,
         eigenvalues_index_begin=eigenvalues_index_begin,
         eigenvalues_index_end=eigenvalues_index_end,
+        tridiag_solver=tridiag_solver,
+        eigenvalues_value_range=eigenvalues_value_range,
     )
     # back-substitute: x = L^-H y
     triangular_solver(Side.Left, UpLo.Lower, Op.ConjTrans, Diag.NonUnit, 1.0,

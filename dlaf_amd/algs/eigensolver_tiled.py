@@ -643,7 +643,8 @@ def _cv(t: torch.Tensor) -> torch.Tensor:
 def hermitian_eigensolver_tiled(uplo: UpLo, mat: Matrix, grid: CommGrid,
                                 band: int,
                                 eigenvalues_index_begin: int = 0,
-                                eigenvalues_index_end: Optional[int] = None
+                                eigenvalues_index_end: Optional[int] = None,
+                                eigenvalues_value_range=None
                                 ) -> Tuple[torch.Tensor, Matrix]:
     """Distributed HEEV with tiled stage 1 and striped eigenvectors.
 
@@ -660,12 +661,16 @@ def hermitian_eigensolver_tiled(uplo: UpLo, mat: Matrix, grid: CommGrid,
     group = grid.full_group
     ib = eigenvalues_index_begin
     ie = n if eigenvalues_index_end is None else eigenvalues_index_end
-    nE = ie - ib
 
     refl = red2band_tiled(mat, band, grid)
 
     from .band2tridiag import chase_band
     tri = chase_band(extract_band_tiled(mat, band, grid), band)
+    if eigenvalues_value_range is not None:
+        # Sturm counts on the replicated tridiagonal: same range on all ranks
+        from .eigensolver import _value_range_indices
+        ib, ie = _value_range_indices(tri, eigenvalues_value_range, dev)
+    nE = ie - ib
 
     import os
     rb = int(os.environ.get("DLAF_DC_ROW_BLOCK", "4096"))

@@ -14,6 +14,9 @@ def extra(p):
     p.add_argument("--band-size", type=int, default=0)
     p.add_argument("--eigenvalues-only", action="store_true",
                    help="hermitian_eigenvalues: Sturm bisection, no eigenvectors")
+    p.add_argument("--tridiag-solver", choices=["dc", "bisect"], default="dc",
+                   help="tridiagonal stage: divide and conquer, or bisection "
+                        "+ inverse iteration (local grids only)")
 
 
 def setup(ctx):
@@ -25,7 +28,8 @@ def run(ctx, st):
     band = ctx.opts.band_size or None
     if ctx.opts.eigenvalues_only:
         return hermitian_eigenvalues(UpLo.Lower, st["a"], ctx.comm_grid, band=band)
-    w, e = hermitian_eigensolver(UpLo.Lower, st["a"], ctx.comm_grid, band=band)
+    w, e = hermitian_eigensolver(UpLo.Lower, st["a"], ctx.comm_grid, band=band,
+                                 tridiag_solver=ctx.opts.tridiag_solver)
     return (w, e)
 
 

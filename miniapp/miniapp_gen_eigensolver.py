@@ -12,6 +12,9 @@ from dlaf_amd import (UpLo, hermitian_generalized_eigensolver,
 def extra(p):
     p.add_argument("--eigenvalues-only", action="store_true",
                    help="hermitian_generalized_eigenvalues: no eigenvectors")
+    p.add_argument("--tridiag-solver", choices=["dc", "bisect"], default="dc",
+                   help="tridiagonal stage: divide and conquer, or bisection "
+                        "+ inverse iteration (local grids only)")
 
 
 def setup(ctx):
@@ -25,7 +28,9 @@ def run(ctx, st):
     if ctx.opts.eigenvalues_only:
         return hermitian_generalized_eigenvalues(UpLo.Lower, st["a"], st["b"],
                                                  ctx.comm_grid)
-    return hermitian_generalized_eigensolver(UpLo.Lower, st["a"], st["b"], ctx.comm_grid)
+    return hermitian_generalized_eigensolver(
+        UpLo.Lower, st["a"], st["b"], ctx.comm_grid,
+        tridiag_solver=ctx.opts.tridiag_solver)
 
 
 def check(ctx, st, result):

@@ -26,6 +26,7 @@ setup(
                 "csrc/panel_qr.hip",
                 "csrc/secular.hip",
                 "csrc/bisect.hip",
+                "csrc/invit.hip",
                 "csrc/rocblas_batch.cpp",
                 "csrc/chase_gpu.hip",
             ],
