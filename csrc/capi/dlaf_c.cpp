@@ -15,6 +15,7 @@
 #include <pybind11/numpy.h>
 
 #include <dlfcn.h>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -157,6 +158,26 @@ int run_geigvals(int ctx, char uplo, void* a, const struct DLAF_descriptor& da,
   } catch (const std::exception& e) {
     std::fprintf(stderr, "dlaf_c: gen eigenvalues failed: %s\n", e.what());
     return -1;
+  }
+}
+
+// norm of the leading m x n part of the caller's (read-only) buffer
+double run_norm(int ctx, char norm, char structure, char uplo, char diag,
+                int m, int n, const void* a, const struct DLAF_descriptor& d,
+                const char* dtype) {
+  Gil g;
+  try {
+    auto arr = np_view(ctx, const_cast<void*>(a), d, dtype);
+    struct DLAF_descriptor sub = d;
+    sub.m = m;
+    sub.n = n;
+    return capi_->attr("dlaf_matrix_norm")(
+        ctx, std::string(1, norm), std::string(1, structure),
+        std::string(1, uplo), std::string(1, diag), arr, desc_obj(sub))
+        .cast<double>();
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: matrix norm failed: %s\n", e.what());
+    return std::nan("");
   }
 }
 
@@ -380,6 +401,37 @@ void dlaf_pdsygvd(char uplo, int n, double* a, int ia, int ja,
   *info = dlaf_symmetric_generalized_eigensolver_d(
       sl_grid(), uplo, a, from_sl(n, desca), b, from_sl(n, descb), w, z,
       from_sl(n, descz));
+}
+
+double dlaf_pdlange(char norm, int m, int n, const double* a, int ia, int ja,
+                    const int desca[9]) {
+  (void)ia; (void)ja;
+  return run_norm(sl_grid(), norm, 'G', 'L', 'N', m, n, a, from_sl(n, desca),
+                  "float64");
+}
+double dlaf_pzlange(char norm, int m, int n, const dlaf_complex_z* a, int ia,
+                    int ja, const int desca[9]) {
+  (void)ia; (void)ja;
+  return run_norm(sl_grid(), norm, 'G', 'L', 'N', m, n, a, from_sl(n, desca),
+                  "complex128");
+}
+double dlaf_pdlansy(char norm, char uplo, int n, const double* a, int ia,
+                    int ja, const int desca[9]) {
+  (void)ia; (void)ja;
+  return run_norm(sl_grid(), norm, 'H', uplo, 'N', n, n, a, from_sl(n, desca),
+                  "float64");
+}
+double dlaf_pzlanhe(char norm, char uplo, int n, const dlaf_complex_z* a,
+                    int ia, int ja, const int desca[9]) {
+  (void)ia; (void)ja;
+  return run_norm(sl_grid(), norm, 'H', uplo, 'N', n, n, a, from_sl(n, desca),
+                  "complex128");
+}
+double dlaf_pdlantr(char norm, char uplo, char diag, int m, int n,
+                    const double* a, int ia, int ja, const int desca[9]) {
+  (void)ia; (void)ja;
+  return run_norm(sl_grid(), norm, 'T', uplo, diag, m, n, a,
+                  from_sl(n, desca), "float64");
 }
 
 }  // extern "C"

@@ -466,6 +466,51 @@ void band_chase_gpu(torch::Tensor band, int64_t b, torch::Tensor vstore,
   });
 }
 
+// ---- matrix norms over the local tile storage (norms.hip) ----
+
+// (rows [tiles_r*mb], cols [tiles_c*nb], scal [4]) of dlaf::matrix_norms for
+// a contiguous device storage [tiles_r, tiles_c, mb, nb]; float64, on the
+// storage's device.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> matrix_norms(
+    torch::Tensor storage, int64_t m, int64_t n, int64_t gr0, int64_t grs,
+    int64_t gc0, int64_t gcs, int64_t structure, int64_t uplo,
+    bool unit_diag) {
+  TORCH_CHECK(storage.is_cuda() && storage.dim() == 4 &&
+              storage.is_contiguous(),
+              "storage must be a contiguous [tiles_r, tiles_c, mb, nb] "
+              "device tensor");
+  TORCH_CHECK(structure >= 0 && structure <= 2 && (uplo == 0 || uplo == 1),
+              "bad structure / uplo");
+  const int64_t tr = storage.size(0), tc = storage.size(1),
+                mb = storage.size(2), nb = storage.size(3);
+  TORCH_CHECK(tr > 0 && tc > 0 && mb > 0 && nb > 0, "empty storage");
+  TORCH_CHECK(m >= 0 && n >= 0 && gr0 >= 0 && gc0 >= 0 && grs >= 1 && gcs >= 1,
+              "bad geometry");
+  TORCH_CHECK(tr * mb < (1LL << 31) && tc * nb < (1LL << 31) &&
+              (gr0 + tr * grs) * mb < (1LL << 40) &&
+              (gc0 + tc * gcs) * nb < (1LL << 40) &&
+              tr * tc * ((mb + dlaf::kNormStripRows - 1) /
+                         dlaf::kNormStripRows) < (1LL << 31),
+              "matrix too large for the norm kernel");
+  auto opts = storage.options().dtype(torch::kFloat64);
+  auto rows = torch::empty({tr * mb}, opts);
+  auto cols = torch::empty({tc * nb}, opts);
+  auto scal = torch::empty({4}, opts);
+  auto work = torch::empty(
+      {dlaf::matrix_norms_work_size((int)tr, (int)tc, (int)mb, (int)nb)}, opts);
+  dispatch_dtype(storage.scalar_type(), [&](auto tag) {
+    using S = typename decltype(tag)::type;
+    dlaf::matrix_norms(ptr<const S>(storage), (int)tr, (int)tc, (int)mb,
+                       (int)nb, m, n, (int)gr0, (int)grs, (int)gc0, (int)gcs,
+                       (int)structure, (int)uplo, unit_diag ? 1 : 0,
+                       rows.data_ptr<double>(), cols.data_ptr<double>(),
+                       scal.data_ptr<double>(), work.data_ptr<double>(),
+                       cur_stream());
+  });
+  HIP_CHECK(hipGetLastError());
+  return {rows, cols, scal};
+}
+
 }  // namespace
 
 // csrc/band_chase.cpp
@@ -488,6 +533,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "column (host loop for CPU tensors)",
         py::arg("d"), py::arg("e"), py::arg("lam"), py::arg("tol"),
         py::arg("X"), py::arg("work"));
+  m.def("matrix_norms", &matrix_norms,
+        "one-pass (row sums, column sums, [max, small, medium, big]) of a "
+        "local tile storage, masked by global extent and structure",
+        py::arg("storage"), py::arg("m"), py::arg("n"), py::arg("gr0"),
+        py::arg("grs"), py::arg("gc0"), py::arg("gcs"), py::arg("structure"),
+        py::arg("uplo"), py::arg("unit_diag"));
   m.def("sturm_interval", &sturm_interval,
         "(gl, gu, pivmin): widened Gershgorin interval and pivot floor");
   m.def("dc_deflate_scan", &dc_deflate_scan,

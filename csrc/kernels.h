@@ -137,4 +137,24 @@ void tridiag_shifted_solve(const double* d, const double* e, int n,
                            long long ldx, double* work, long long cols,
                            hipStream_t stream);
 
+// ---- matrix norms over the local tile storage, csrc/norms.hip ----
+// One pass over a [tiles_r, tiles_c, mb, nb] storage: rows[tiles_r * mb] and
+// cols[tiles_c * nb] get the absolute sums per LOCAL row / column, scal[4] =
+// (max |a|, Blue's small, medium, big sums of squares). Local tile l sits at
+// global tile g0 + l * gs; elements at global (row, col) outside (m, n) or
+// outside the structure's triangle count as absent. structure: 0 general,
+// 1 hermitian (off-diagonal a_ij stands for a_ji too: its |a_ij| goes to the
+// row AND the column sum, twice into the squares; the diagonal counts
+// |Re a_ii| once, in the column sum), 2 triangular (unit_diag: diagonal = 1).
+// uplo: 0 Lower, 1 Upper. work holds matrix_norms_work_size() doubles and
+// needs no clearing. tiles_r <= 0 or tiles_c <= 0 launches nothing.
+constexpr int kNormStripRows = 64;
+int64_t matrix_norms_work_size(int tiles_r, int tiles_c, int mb, int nb);
+template <typename S>
+void matrix_norms(const S* a, int tiles_r, int tiles_c, int mb, int nb,
+                  int64_t m, int64_t n, int gr0, int grs, int gc0, int gcs,
+                  int structure, int uplo, int unit_diag, double* rows,
+                  double* cols, double* scal, double* work,
+                  hipStream_t stream);
+
 }  // namespace dlaf

@@ -18,7 +18,7 @@ Public API (mirrors the reference's free-function API):
     triangular_inverse, generalized_to_standard, reduction_to_band,
     band_to_tridiagonal, tridiagonal_eigensolver, bt_band_to_tridiagonal,
     bt_reduction_to_band, hermitian_eigensolver, hermitian_generalized_eigensolver,
-    max_norm, and the eigenvalues-only drivers tridiagonal_eigenvalues,
+    max_norm, matrix_norm, and the eigenvalues-only drivers tridiagonal_eigenvalues,
     tridiagonal_eigenvalue_count, hermitian_eigenvalues,
     hermitian_generalized_eigenvalues, and the partial-spectrum eigenvector
     solvers tridiagonal_eigenvectors, tridiagonal_eigensolver_bisect
@@ -38,7 +38,7 @@ from .algs.multiplication import (  # noqa: F401
 )
 from .algs.inverse import triangular_inverse, inverse_from_cholesky_factor  # noqa: F401
 from .algs.gen_to_std import generalized_to_standard  # noqa: F401
-from .algs.norm import max_norm  # noqa: F401
+from .algs.norm import max_norm, matrix_norm  # noqa: F401
 from .algs.eigensolver import (  # noqa: F401
     hermitian_eigensolver,
     hermitian_generalized_eigensolver,

@@ -23,6 +23,7 @@ from .tridiag_invit import tridiagonal_eigensolver_bisect
 from .cholesky import cholesky_factorization
 from .gen_to_std import generalized_to_standard
 from .triangular import triangular_solver
+from . import _scaling
 
 
 def get_band_size(nb: int) -> int:
@@ -68,7 +69,26 @@ def hermitian_eigensolver(
     ``eigenvalues_value_range=(vl, vu)`` selects the eigenvalues in the
     HALF-OPEN interval ``[vl, vu)`` instead of an index range (the two are
     mutually exclusive), as in ``hermitian_eigenvalues``.
+
+    Safe at any scale: a matrix whose max-norm is outside the safe range of
+    its real type is scaled by a power of two first and the eigenvalues are
+    scaled back (``_scaling.py``); inside the range nothing is touched.
     """
+    e = 0
+    d = mat.dist
+    if uplo == UpLo.Lower and d.m == d.n and d.mb == d.nb:
+        e = _scaling.scale_hermitian(
+            mat, grid if grid is not None else mat.grid)
+    w, evecs = _hermitian_eigensolver(
+        uplo, mat, grid, band, eigenvalues_index_begin, eigenvalues_index_end,
+        tridiag_solver, _scaling.scale_range(eigenvalues_value_range, e))
+    return (_scaling.scale_values(w, -e) if e else w), evecs
+
+
+def _hermitian_eigensolver(uplo, mat, grid, band, eigenvalues_index_begin,
+                           eigenvalues_index_end, tridiag_solver,
+                           eigenvalues_value_range):
+    """``hermitian_eigensolver`` on a matrix already in the safe range."""
     from ..core.asserts import dlaf_assert
     dlaf_assert(uplo == UpLo.Lower,
                 "only Lower implemented (as the reference miniapps)")
@@ -212,20 +232,36 @@ def hermitian_generalized_eigensolver(
     factor when ``factorized``); ``mat_a`` is overwritten. Reference:
     ``eigensolver/gen_eigensolver/impl.h:30-104``. ``tridiag_solver`` and
     ``eigenvalues_value_range`` as in ``hermitian_eigensolver``.
+
+    A and B (or the given factor) are scaled independently when their norms
+    are outside the safe range; eigenvalues, eigenvectors and the factor left
+    in ``mat_b`` are those of the caller's A and B.
     """
     assert uplo == UpLo.Lower
     g = grid if grid is not None else mat_a.grid
-    if not factorized:
-        cholesky_factorization(UpLo.Lower, mat_b, g)
-    generalized_to_standard(UpLo.Lower, mat_a, mat_b, g)
-    w, evecs = hermitian_eigensolver(
-        UpLo.Lower, mat_a, g, band=band,
-        eigenvalues_index_begin=eigenvalues_index_begin,
-        eigenvalues_index_end=eigenvalues_index_end,
-        tridiag_solver=tridiag_solver,
-        eigenvalues_value_range=eigenvalues_value_range,
-    )
-    # back-substitute: x = L^-H y
-    triangular_solver(Side.Left, UpLo.Lower, Op.ConjTrans, Diag.NonUnit, 1.0,
-                      mat_b, evecs, g)
+    ea, k = _scaling.scale_generalized(mat_a, mat_b, g, factorized)
+    # mat_b holds 4^k B until it is factorized, 2^k L from then on; whatever
+    # happens, the caller gets it back in its own units
+    undo = k if factorized else 2 * k
+    try:
+        if not factorized:
+            cholesky_factorization(UpLo.Lower, mat_b, g)
+            undo = k
+        generalized_to_standard(UpLo.Lower, mat_a, mat_b, g)
+        w, evecs = hermitian_eigensolver(
+            UpLo.Lower, mat_a, g, band=band,
+            eigenvalues_index_begin=eigenvalues_index_begin,
+            eigenvalues_index_end=eigenvalues_index_end,
+            tridiag_solver=tridiag_solver,
+            eigenvalues_value_range=_scaling.scale_range(
+                eigenvalues_value_range, ea - 2 * k),
+        )
+        # back-substitute: x = L^-H y
+        triangular_solver(Side.Left, UpLo.Lower, Op.ConjTrans, Diag.NonUnit,
+                          1.0, mat_b, evecs, g)
+    finally:
+        _scaling.scale_matrix(mat_b, -undo)
+    _scaling.scale_matrix(evecs, k)  # x = 2^k x'
+    if ea or k:
+        w = _scaling.scale_values(w, 2 * k - ea)
     return w, evecs

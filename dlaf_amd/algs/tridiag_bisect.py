@@ -159,7 +159,25 @@ def hermitian_eigenvalues(
     interval ``[vl, vu)`` — note this differs from LAPACK's ``(vl, vu]``. The
     two are mutually exclusive. Returns ``w`` ascending in the real dtype of
     ``mat``; identical on every rank of a distributed grid.
+
+    Safe at any scale, by the same power-of-two scaling as
+    ``hermitian_eigensolver``.
     """
+    from . import _scaling
+    e = 0
+    d = mat.dist
+    if uplo == UpLo.Lower and d.m == d.n and d.mb == d.nb:
+        e = _scaling.scale_hermitian(
+            mat, grid if grid is not None else mat.grid)
+    w = _hermitian_eigenvalues(
+        uplo, mat, grid, band, eigenvalues_index_begin, eigenvalues_index_end,
+        _scaling.scale_range(eigenvalues_value_range, e))
+    return _scaling.scale_values(w, -e) if e else w
+
+
+def _hermitian_eigenvalues(uplo, mat, grid, band, eigenvalues_index_begin,
+                           eigenvalues_index_end, eigenvalues_value_range):
+    """``hermitian_eigenvalues`` on a matrix already in the safe range."""
     from .eigensolver import get_band_size
     dlaf_assert(uplo == UpLo.Lower,
                 "only Lower implemented (as the reference miniapps)")
@@ -241,13 +259,23 @@ def hermitian_generalized_eigenvalues(
     """
     from .cholesky import cholesky_factorization
     from .gen_to_std import generalized_to_standard
+    from . import _scaling
     dlaf_assert(uplo == UpLo.Lower, "only Lower implemented")
     g = grid if grid is not None else mat_a.grid
-    if not factorized:
-        cholesky_factorization(UpLo.Lower, mat_b, g)
-    generalized_to_standard(UpLo.Lower, mat_a, mat_b, g)
-    return hermitian_eigenvalues(
-        UpLo.Lower, mat_a, g, band=band,
-        eigenvalues_index_begin=eigenvalues_index_begin,
-        eigenvalues_index_end=eigenvalues_index_end,
-        eigenvalues_value_range=eigenvalues_value_range)
+    # A, B (or the factor) scaled as in hermitian_generalized_eigensolver
+    ea, k = _scaling.scale_generalized(mat_a, mat_b, g, factorized)
+    undo = k if factorized else 2 * k  # 4^k B until factorized, then 2^k L
+    try:
+        if not factorized:
+            cholesky_factorization(UpLo.Lower, mat_b, g)
+            undo = k
+        generalized_to_standard(UpLo.Lower, mat_a, mat_b, g)
+        w = hermitian_eigenvalues(
+            UpLo.Lower, mat_a, g, band=band,
+            eigenvalues_index_begin=eigenvalues_index_begin,
+            eigenvalues_index_end=eigenvalues_index_end,
+            eigenvalues_value_range=_scaling.scale_range(
+                eigenvalues_value_range, ea - 2 * k))
+    finally:
+        _scaling.scale_matrix(mat_b, -undo)
+    return _scaling.scale_values(w, 2 * k - ea) if (ea or k) else w

@@ -3,8 +3,9 @@
 Counterpart of the reference's C API (``include/dlaf_c/*``, ``src/c_api/*``):
 grid management by integer context, ScaLAPACK-style descriptors, and
 ``p?potrf / p?potri / p?trtri / p?syevd / p?heevd / p?sygvd / p?hegvd``
-entry points operating on the caller's LOCAL block-cyclic column-major
-buffer (numpy or torch). Each call wraps the buffer into a tiled ``Matrix``
+entry points and the norms ``p?lange / p?lansy / p?lanhe / p?lantr``, all
+operating on the caller's LOCAL block-cyclic column-major buffer (numpy or
+torch). Each call wraps the buffer into a tiled ``Matrix``
 (mirrored to the GPU when available), runs the native algorithm, and copies
 the result back — the flow of the reference's ``src/c_api/eigensolver/
 eigensolver.h:30-73`` (host matrix -> MatrixMirror -> algorithm -> copy back).
@@ -31,6 +32,7 @@ from .algs.inverse import inverse_from_cholesky_factor, triangular_inverse
 from .algs.eigensolver import hermitian_eigensolver, hermitian_generalized_eigensolver
 from .algs.tridiag_bisect import (hermitian_eigenvalues,
                                   hermitian_generalized_eigenvalues)
+from .algs.norm import matrix_norm
 
 
 @dataclass
@@ -312,6 +314,35 @@ def dlaf_hermitian_generalized_eigenvalues(ctx: int, uplo: str, a_local,
     return 0
 
 
+# LAPACK norm characters -> matrix_norm names
+_NORM_CHAR = {"M": "max", "1": "one", "O": "one", "I": "inf", "F": "fro",
+              "E": "fro"}
+_STRUCT_CHAR = {"G": "general", "H": "hermitian", "S": "hermitian",
+                "T": "triangular"}
+
+
+def dlaf_matrix_norm(ctx: int, norm: str, structure: str, uplo: Optional[str],
+                     diag: str, a_local, desc: DLAF_descriptor) -> float:
+    """Norm of the matrix in ``a_local`` (which is only read).
+
+    norm: 'M', '1' / 'O', 'I', 'F' / 'E' (LAPACK) or a ``matrix_norm`` name;
+    structure: 'G'eneral, 'H'ermitian / 'S'ymmetric (real), 'T'riangular or a
+    ``matrix_norm`` name; uplo 'L' / 'U' (ignored for general); diag 'N' /
+    'U' (triangular only). Every rank of the grid gets the same value.
+    """
+    grid = _grid(ctx)
+    mat = _wrap_local(a_local, desc, grid, _device_for(grid))
+    name = _NORM_CHAR.get(str(norm).upper(), norm)
+    struct = _STRUCT_CHAR.get(str(structure).upper(), structure)
+    ul = None
+    if struct != "general":
+        ul = UpLo.Upper if str(uplo).upper() == "U" else UpLo.Lower
+    return matrix_norm(name, mat, uplo=ul, structure=struct,
+                       diag=Diag.Unit if str(diag).upper() == "U"
+                       else Diag.NonUnit,
+                       grid=grid if grid.distributed else None)
+
+
 # ---- ScaLAPACK-style shims (reference dlaf_c/...: dlaf_p{s,d,c,z}potrf etc.) ----
 
 def _sl_desc(n, mb, nb, uplo_n=None, m=None) -> DLAF_descriptor:
@@ -347,6 +378,37 @@ def pXsygvd(ctx: int, uplo: str, n: int, a_local, desca, b_local, descb,
                                                   b_local, descb, w_out, z_local, descz)
 
 
+def _norm_desc(desca: DLAF_descriptor, m: int, n: int) -> DLAF_descriptor:
+    """desca restricted to its leading m x n part (ia = ja = 1)."""
+    assert 0 <= m <= desca.m and 0 <= n <= desca.n, (m, n, desca)
+    return DLAF_descriptor(m, n, desca.mb, desca.nb, desca.isrc, desca.jsrc,
+                           1, 1, desca.ld)
+
+
+def pXlange(ctx: int, norm: str, m: int, n: int, a_local, ia: int, ja: int,
+            desca: DLAF_descriptor) -> float:
+    assert (ia, ja) == (1, 1)
+    return dlaf_matrix_norm(ctx, norm, "G", None, "N", a_local,
+                            _norm_desc(desca, m, n))
+
+
+def pXlanhe(ctx: int, norm: str, uplo: str, n: int, a_local, ia: int, ja: int,
+            desca: DLAF_descriptor) -> float:
+    assert (ia, ja) == (1, 1)
+    return dlaf_matrix_norm(ctx, norm, "H", uplo, "N", a_local,
+                            _norm_desc(desca, n, n))
+
+
+pXlansy = pXlanhe  # real symmetric; complex-symmetric zlansy is not provided
+
+
+def pXlantr(ctx: int, norm: str, uplo: str, diag: str, m: int, n: int, a_local,
+            ia: int, ja: int, desca: DLAF_descriptor) -> float:
+    assert (ia, ja) == (1, 1)
+    return dlaf_matrix_norm(ctx, norm, "T", uplo, diag, a_local,
+                            _norm_desc(desca, m, n))
+
+
 # dtype-suffixed aliases matching the reference's C symbol names
 dlaf_pdpotrf = dlaf_pspotrf = dlaf_pcpotrf = dlaf_pzpotrf = pXpotrf
 dlaf_pdpotri = dlaf_pspotri = dlaf_pcpotri = dlaf_pzpotri = pXpotri
@@ -355,3 +417,7 @@ dlaf_pdsyevd = dlaf_pssyevd = pXsyevd
 dlaf_pcheevd = dlaf_pzheevd = pXsyevd
 dlaf_pdsygvd = dlaf_pssygvd = pXsygvd
 dlaf_pchegvd = dlaf_pzhegvd = pXsygvd
+dlaf_pdlange = dlaf_pslange = dlaf_pclange = dlaf_pzlange = pXlange
+dlaf_pdlansy = dlaf_pslansy = pXlansy
+dlaf_pclanhe = dlaf_pzlanhe = pXlanhe
+dlaf_pdlantr = dlaf_pslantr = dlaf_pclantr = dlaf_pzlantr = pXlantr

@@ -124,6 +124,23 @@ void dlaf_pdsygvd(char uplo, int n, double* a, int ia, int ja, const int desca[9
                   double* b, int ib, int jb, const int descb[9],
                   double* w, double* z, int iz, int jz, const int descz[9], int* info);
 
+
+/* Matrix norms (ScaLAPACK p?lange / p?lansy / p?lanhe / p?lantr) of the
+ * leading m x n (n x n) part of a, which is only read. norm: 'M' max |a_ij|,
+ * '1' or 'O' one-norm, 'I' infinity-norm, 'F' or 'E' Frobenius. lansy / lanhe
+ * read the uplo triangle only; lantr ignores the other triangle and with
+ * diag = 'U' counts the diagonal as 1. ia = ja = 1. Returns NaN on error. */
+double dlaf_pdlange(char norm, int m, int n, const double* a, int ia, int ja,
+                    const int desca[9]);
+double dlaf_pzlange(char norm, int m, int n, const dlaf_complex_z* a, int ia,
+                    int ja, const int desca[9]);
+double dlaf_pdlansy(char norm, char uplo, int n, const double* a, int ia,
+                    int ja, const int desca[9]);
+double dlaf_pzlanhe(char norm, char uplo, int n, const dlaf_complex_z* a,
+                    int ia, int ja, const int desca[9]);
+double dlaf_pdlantr(char norm, char uplo, char diag, int m, int n,
+                    const double* a, int ia, int ja, const int desca[9]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ setup(
                 "csrc/secular.hip",
                 "csrc/bisect.hip",
                 "csrc/invit.hip",
+                "csrc/norms.hip",
                 "csrc/rocblas_batch.cpp",
                 "csrc/chase_gpu.hip",
             ],
