@@ -181,6 +181,51 @@ double run_norm(int ctx, char norm, char structure, char uplo, char diag,
   }
 }
 
+// rcond estimates of the leading n x n part of the caller's (read-only)
+// buffer: trcon when norm != 0, else pocon with the given anorm
+int run_rcond(int ctx, char norm, char uplo, char diag, int n, double anorm,
+              const void* a, const struct DLAF_descriptor& d,
+              const char* dtype, double* rcond) {
+  Gil g;
+  try {
+    auto arr = np_view(ctx, const_cast<void*>(a), d, dtype);
+    struct DLAF_descriptor sub = d;
+    sub.m = sub.n = n;
+    if (norm)
+      *rcond = capi_->attr("dlaf_triangular_rcond")(
+          ctx, std::string(1, norm), std::string(1, uplo),
+          std::string(1, diag), arr, desc_obj(sub)).cast<double>();
+    else
+      *rcond = capi_->attr("dlaf_cholesky_rcond")(
+          ctx, std::string(1, uplo), arr, desc_obj(sub), anorm).cast<double>();
+    return 0;
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: condition estimate failed: %s\n", e.what());
+    *rcond = std::nan("");
+    return -1;
+  }
+}
+
+int run_potrs(int ctx, char uplo, int n, int nrhs, const void* a,
+              const struct DLAF_descriptor& da, void* b,
+              const struct DLAF_descriptor& db, const char* dtype) {
+  Gil g;
+  try {
+    auto av = np_view(ctx, const_cast<void*>(a), da, dtype);
+    auto bv = np_view(ctx, b, db, dtype);
+    struct DLAF_descriptor sa = da, sb = db;
+    sa.m = sa.n = n;
+    sb.m = n;
+    sb.n = nrhs;
+    return capi_->attr("dlaf_cholesky_solve")(
+        ctx, std::string(1, uplo), av, desc_obj(sa), bv, desc_obj(sb))
+        .cast<int>();
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: cholesky solve failed: %s\n", e.what());
+    return -1;
+  }
+}
+
 struct DLAF_descriptor from_sl(int n, const int d[9], int m = -1) {
   struct DLAF_descriptor out;
   out.m = m >= 0 ? m : d[2];
@@ -432,6 +477,40 @@ double dlaf_pdlantr(char norm, char uplo, char diag, int m, int n,
   (void)ia; (void)ja;
   return run_norm(sl_grid(), norm, 'T', uplo, diag, m, n, a,
                   from_sl(n, desca), "float64");
+}
+
+void dlaf_pdpocon(char uplo, int n, const double* a, int ia, int ja,
+                  const int desca[9], double anorm, double* rcond, int* info) {
+  (void)ia; (void)ja;
+  *info = run_rcond(sl_grid(), 0, uplo, 'N', n, anorm, a, from_sl(n, desca),
+                    "float64", rcond);
+}
+void dlaf_pzpocon(char uplo, int n, const dlaf_complex_z* a, int ia, int ja,
+                  const int desca[9], double anorm, double* rcond, int* info) {
+  (void)ia; (void)ja;
+  *info = run_rcond(sl_grid(), 0, uplo, 'N', n, anorm, a, from_sl(n, desca),
+                    "complex128", rcond);
+}
+void dlaf_pdtrcon(char norm, char uplo, char diag, int n, const double* a,
+                  int ia, int ja, const int desca[9], double* rcond,
+                  int* info) {
+  (void)ia; (void)ja;
+  *info = run_rcond(sl_grid(), norm, uplo, diag, n, 0.0, a, from_sl(n, desca),
+                    "float64", rcond);
+}
+void dlaf_pztrcon(char norm, char uplo, char diag, int n,
+                  const dlaf_complex_z* a, int ia, int ja, const int desca[9],
+                  double* rcond, int* info) {
+  (void)ia; (void)ja;
+  *info = run_rcond(sl_grid(), norm, uplo, diag, n, 0.0, a, from_sl(n, desca),
+                    "complex128", rcond);
+}
+void dlaf_pdpotrs(char uplo, int n, int nrhs, const double* a, int ia, int ja,
+                  const int desca[9], double* b, int ib, int jb,
+                  const int descb[9], int* info) {
+  (void)ia; (void)ja; (void)ib; (void)jb;
+  *info = run_potrs(sl_grid(), uplo, n, nrhs, a, from_sl(n, desca), b,
+                    from_sl(nrhs, descb), "float64");
 }
 
 }  // extern "C"

@@ -511,6 +511,43 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> matrix_norms(
   return {rows, cols, scal};
 }
 
+// ---- triangular solve for one vector over the tile storage (trsv.hip) ----
+
+// op(T) x = b in place on x [nt * nb]; storage [nt, nt, nb, nb] holds T in
+// its uplo triangle, dinv [nt, nb, nb] the inverses of its diagonal tiles.
+void trsv_tiles(torch::Tensor storage, torch::Tensor dinv, torch::Tensor x,
+                int64_t n, int64_t uplo, int64_t op) {
+  TORCH_CHECK(storage.is_cuda() && storage.dim() == 4 &&
+              storage.is_contiguous() && storage.size(0) == storage.size(1) &&
+              storage.size(2) == storage.size(3),
+              "storage must be a contiguous [nt, nt, nb, nb] device tensor");
+  const int64_t nt = storage.size(0), nb = storage.size(2);
+  TORCH_CHECK(nb > 0 && nt * nb < (1LL << 31) && nt * nt < (1LL << 20),
+              "matrix too large for the solve kernel");
+  TORCH_CHECK(n >= 0 && n <= nt * nb && n > (nt - 1) * nb,
+              "n does not match the storage");
+  TORCH_CHECK(dinv.dim() == 3 && dinv.is_contiguous() && dinv.size(0) == nt &&
+              dinv.size(1) == nb && dinv.size(2) == nb &&
+              dinv.scalar_type() == storage.scalar_type() &&
+              dinv.device() == storage.device(),
+              "dinv must be contiguous [nt, nb, nb] like the storage");
+  TORCH_CHECK(x.dim() == 1 && x.is_contiguous() && x.size(0) == nt * nb &&
+              x.scalar_type() == storage.scalar_type() &&
+              x.device() == storage.device(),
+              "x must be contiguous [nt * nb] like the storage");
+  TORCH_CHECK((uplo == 0 || uplo == 1) && op >= OP_N && op <= OP_C,
+              "bad uplo / op");
+  if (nt == 0) return;
+  auto work = torch::empty({nb}, x.options());
+  dispatch_dtype(storage.scalar_type(), [&](auto tag) {
+    using S = typename decltype(tag)::type;
+    dlaf::trsv_tiles(ptr<const S>(storage), ptr<const S>(dinv), ptr<S>(x),
+                     ptr<S>(work), (int)nt, (int)nb, n, (int)uplo, (int)op,
+                     cur_stream());
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
 
 // csrc/band_chase.cpp
@@ -539,6 +576,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("storage"), py::arg("m"), py::arg("n"), py::arg("gr0"),
         py::arg("grs"), py::arg("gc0"), py::arg("gcs"), py::arg("structure"),
         py::arg("uplo"), py::arg("unit_diag"));
+  m.def("trsv_tiles", &trsv_tiles,
+        "in-place op(T) x = b for one vector over a local tile storage, "
+        "diagonal tiles applied through their inverses",
+        py::arg("storage"), py::arg("dinv"), py::arg("x"), py::arg("n"),
+        py::arg("uplo"), py::arg("op"));
   m.def("sturm_interval", &sturm_interval,
         "(gl, gu, pivmin): widened Gershgorin interval and pivot floor");
   m.def("dc_deflate_scan", &dc_deflate_scan,

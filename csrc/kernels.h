@@ -157,4 +157,16 @@ void matrix_norms(const S* a, int tiles_r, int tiles_c, int mb, int nb,
                   double* cols, double* scal, double* work,
                   hipStream_t stream);
 
+// ---- triangular solve for one vector over the tile storage, csrc/trsv.hip
+// op(T) x = b in place on x [nt * nb], T the uplo (0 Lower, 1 Upper) triangle
+// of the local [nt, nt, nb, nb] storage a, op = OP_N / OP_T / OP_C. dinv
+// [nt, nb, nb] holds the full-tile inverses of the diagonal tiles (built with
+// the Unit / NonUnit choice, so the stored diagonal is never read here); work
+// holds nb elements. Rows and columns at or beyond n (the identity padding of
+// a partial last tile) are neither read into a sum nor written. 2 * nt plain
+// launches on the stream; nt <= 0 or n <= 0 launches nothing.
+template <typename S>
+void trsv_tiles(const S* a, const S* dinv, S* x, S* work, int nt, int nb,
+                int64_t n, int uplo, int op, hipStream_t stream);
+
 }  // namespace dlaf

@@ -21,7 +21,9 @@ Public API (mirrors the reference's free-function API):
     max_norm, matrix_norm, and the eigenvalues-only drivers tridiagonal_eigenvalues,
     tridiagonal_eigenvalue_count, hermitian_eigenvalues,
     hermitian_generalized_eigenvalues, and the partial-spectrum eigenvector
-    solvers tridiagonal_eigenvectors, tridiagonal_eigensolver_bisect
+    solvers tridiagonal_eigenvectors, tridiagonal_eigensolver_bisect, and the
+    condition estimates triangular_rcond, cholesky_rcond (with
+    TriangularVectorSolver, inverse_norm_estimate) and cholesky_solve
 """
 
 from .types import Side, UpLo, Op, Diag  # noqa: F401
@@ -39,6 +41,13 @@ from .algs.multiplication import (  # noqa: F401
 from .algs.inverse import triangular_inverse, inverse_from_cholesky_factor  # noqa: F401
 from .algs.gen_to_std import generalized_to_standard  # noqa: F401
 from .algs.norm import max_norm, matrix_norm  # noqa: F401
+from .algs.condition import (  # noqa: F401
+    TriangularVectorSolver,
+    inverse_norm_estimate,
+    triangular_rcond,
+    cholesky_rcond,
+    cholesky_solve,
+)
 from .algs.eigensolver import (  # noqa: F401
     hermitian_eigensolver,
     hermitian_generalized_eigensolver,

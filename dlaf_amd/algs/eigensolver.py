@@ -23,6 +23,8 @@ from .tridiag_invit import tridiagonal_eigensolver_bisect
 from .cholesky import cholesky_factorization
 from .gen_to_std import generalized_to_standard
 from .triangular import triangular_solver
+from .norm import matrix_norm
+from .condition import warn_if_ill_conditioned
 from . import _scaling
 
 
@@ -225,6 +227,7 @@ def hermitian_generalized_eigensolver(
     eigenvalues_index_end: Optional[int] = None,
     tridiag_solver: str = "dc",
     eigenvalues_value_range: Optional[Tuple[float, float]] = None,
+    warn_b_rcond: bool = False,
 ) -> Tuple[torch.Tensor, Matrix]:
     """Generalized problem A x = lambda B x (B HPD): returns (w, E).
 
@@ -236,6 +239,11 @@ def hermitian_generalized_eigensolver(
     A and B (or the given factor) are scaled independently when their norms
     are outside the safe range; eigenvalues, eigenvectors and the factor left
     in ``mat_b`` are those of the caller's A and B.
+
+    ``warn_b_rcond``: estimate the reciprocal condition number of B from its
+    factor (``cholesky_rcond``) and emit a ``RuntimeWarning`` carrying it when
+    it is below the precision of the dtype. Needs B itself, so it does
+    nothing when ``factorized``.
     """
     assert uplo == UpLo.Lower
     g = grid if grid is not None else mat_a.grid
@@ -245,8 +253,13 @@ def hermitian_generalized_eigensolver(
     undo = k if factorized else 2 * k
     try:
         if not factorized:
+            if warn_b_rcond:
+                bnorm = matrix_norm("one", mat_b, uplo=UpLo.Lower,
+                                    structure="hermitian", grid=g)
             cholesky_factorization(UpLo.Lower, mat_b, g)
             undo = k
+            if warn_b_rcond:
+                warn_if_ill_conditioned(UpLo.Lower, mat_b, bnorm, g, "B")
         generalized_to_standard(UpLo.Lower, mat_a, mat_b, g)
         w, evecs = hermitian_eigensolver(
             UpLo.Lower, mat_a, g, band=band,

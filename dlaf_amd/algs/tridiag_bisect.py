@@ -248,6 +248,7 @@ def hermitian_generalized_eigenvalues(
     eigenvalues_index_begin: int = 0,
     eigenvalues_index_end: Optional[int] = None,
     eigenvalues_value_range: Optional[Tuple[float, float]] = None,
+    warn_b_rcond: bool = False,
 ) -> torch.Tensor:
     """Eigenvalues only of A x = lambda B x (B HPD).
 
@@ -255,10 +256,13 @@ def hermitian_generalized_eigenvalues(
     factor when ``factorized``); ``mat_a`` is overwritten. Cholesky ->
     generalized_to_standard -> ``hermitian_eigenvalues``; there is no
     back-substitution. Range arguments as in ``hermitian_eigenvalues``
-    (value range half-open ``[vl, vu)``).
+    (value range half-open ``[vl, vu)``). ``warn_b_rcond`` as in
+    ``hermitian_generalized_eigensolver``.
     """
     from .cholesky import cholesky_factorization
     from .gen_to_std import generalized_to_standard
+    from .norm import matrix_norm
+    from .condition import warn_if_ill_conditioned
     from . import _scaling
     dlaf_assert(uplo == UpLo.Lower, "only Lower implemented")
     g = grid if grid is not None else mat_a.grid
@@ -267,8 +271,13 @@ def hermitian_generalized_eigenvalues(
     undo = k if factorized else 2 * k  # 4^k B until factorized, then 2^k L
     try:
         if not factorized:
+            if warn_b_rcond:
+                bnorm = matrix_norm("one", mat_b, uplo=UpLo.Lower,
+                                    structure="hermitian", grid=g)
             cholesky_factorization(UpLo.Lower, mat_b, g)
             undo = k
+            if warn_b_rcond:
+                warn_if_ill_conditioned(UpLo.Lower, mat_b, bnorm, g, "B")
         generalized_to_standard(UpLo.Lower, mat_a, mat_b, g)
         w = hermitian_eigenvalues(
             UpLo.Lower, mat_a, g, band=band,

@@ -3,7 +3,8 @@
 Counterpart of the reference's C API (``include/dlaf_c/*``, ``src/c_api/*``):
 grid management by integer context, ScaLAPACK-style descriptors, and
 ``p?potrf / p?potri / p?trtri / p?syevd / p?heevd / p?sygvd / p?hegvd``
-entry points and the norms ``p?lange / p?lansy / p?lanhe / p?lantr``, all
+entry points, the norms ``p?lange / p?lansy / p?lanhe / p?lantr``, the
+condition estimates ``p?pocon / p?trcon`` and the solve ``p?potrs``, all
 operating on the caller's LOCAL block-cyclic column-major buffer (numpy or
 torch). Each call wraps the buffer into a tiled ``Matrix``
 (mirrored to the GPU when available), runs the native algorithm, and copies
@@ -33,6 +34,7 @@ from .algs.eigensolver import hermitian_eigensolver, hermitian_generalized_eigen
 from .algs.tridiag_bisect import (hermitian_eigenvalues,
                                   hermitian_generalized_eigenvalues)
 from .algs.norm import matrix_norm
+from .algs.condition import cholesky_rcond, triangular_rcond, cholesky_solve
 
 
 @dataclass
@@ -343,6 +345,51 @@ def dlaf_matrix_norm(ctx: int, norm: str, structure: str, uplo: Optional[str],
                        grid=grid if grid.distributed else None)
 
 
+def _uplo(uplo: str) -> UpLo:
+    return UpLo.Upper if str(uplo).upper() == "U" else UpLo.Lower
+
+
+def dlaf_cholesky_rcond(ctx: int, uplo: str, a_local, desc: DLAF_descriptor,
+                        anorm: float) -> float:
+    """Estimated reciprocal one-norm condition number of the Hermitian
+    positive definite matrix whose Cholesky factor (as left by
+    ``dlaf_cholesky_factorization``) is in the ``uplo`` triangle of
+    ``a_local``, which is only read. ``anorm`` is the one-norm of the matrix
+    before factorization (``dlaf_matrix_norm(ctx, '1', 'H', uplo, ...)``).
+    Every rank of the grid gets the same value."""
+    grid = _grid(ctx)
+    mat = _wrap_local(a_local, desc, grid, _device_for(grid))
+    return cholesky_rcond(_uplo(uplo), mat, float(anorm),
+                          grid if grid.distributed else None)
+
+
+def dlaf_triangular_rcond(ctx: int, norm: str, uplo: str, diag: str, a_local,
+                          desc: DLAF_descriptor) -> float:
+    """Estimated reciprocal condition number of the triangular matrix in the
+    ``uplo`` triangle of ``a_local`` (only read). norm: '1' / 'O' or 'I'
+    (LAPACK) or ``"one"`` / ``"inf"``; diag 'N' / 'U'."""
+    grid = _grid(ctx)
+    mat = _wrap_local(a_local, desc, grid, _device_for(grid))
+    name = _NORM_CHAR.get(str(norm).upper(), norm)
+    return triangular_rcond(name, _uplo(uplo),
+                            Diag.Unit if str(diag).upper() == "U"
+                            else Diag.NonUnit, mat,
+                            grid if grid.distributed else None)
+
+
+def dlaf_cholesky_solve(ctx: int, uplo: str, a_local, desca: DLAF_descriptor,
+                        b_local, descb: DLAF_descriptor) -> int:
+    """Solve A X = B with the Cholesky factor of A in the ``uplo`` triangle of
+    ``a_local`` (only read); ``b_local`` is overwritten with X."""
+    grid = _grid(ctx)
+    dev = _device_for(grid)
+    fac = _wrap_local(a_local, desca, grid, dev)
+    rhs = _wrap_local(b_local, descb, grid, dev)
+    cholesky_solve(_uplo(uplo), fac, rhs, grid if grid.distributed else None)
+    _unwrap_local(rhs, b_local)
+    return 0
+
+
 # ---- ScaLAPACK-style shims (reference dlaf_c/...: dlaf_p{s,d,c,z}potrf etc.) ----
 
 def _sl_desc(n, mb, nb, uplo_n=None, m=None) -> DLAF_descriptor:
@@ -409,6 +456,30 @@ def pXlantr(ctx: int, norm: str, uplo: str, diag: str, m: int, n: int, a_local,
                             _norm_desc(desca, m, n))
 
 
+def pXpocon(ctx: int, uplo: str, n: int, a_local, ia: int, ja: int,
+            desca: DLAF_descriptor, anorm: float) -> float:
+    """rcond of p?pocon (its workspace arguments have no counterpart)."""
+    assert (ia, ja) == (1, 1)
+    return dlaf_cholesky_rcond(ctx, uplo, a_local, _norm_desc(desca, n, n),
+                               anorm)
+
+
+def pXtrcon(ctx: int, norm: str, uplo: str, diag: str, n: int, a_local,
+            ia: int, ja: int, desca: DLAF_descriptor) -> float:
+    """rcond of p?trcon."""
+    assert (ia, ja) == (1, 1)
+    return dlaf_triangular_rcond(ctx, norm, uplo, diag, a_local,
+                                 _norm_desc(desca, n, n))
+
+
+def pXpotrs(ctx: int, uplo: str, n: int, nrhs: int, a_local, ia: int, ja: int,
+            desca: DLAF_descriptor, b_local, ib: int, jb: int,
+            descb: DLAF_descriptor) -> int:
+    assert (ia, ja) == (1, 1) and (ib, jb) == (1, 1)
+    return dlaf_cholesky_solve(ctx, uplo, a_local, _norm_desc(desca, n, n),
+                               b_local, _norm_desc(descb, n, nrhs))
+
+
 # dtype-suffixed aliases matching the reference's C symbol names
 dlaf_pdpotrf = dlaf_pspotrf = dlaf_pcpotrf = dlaf_pzpotrf = pXpotrf
 dlaf_pdpotri = dlaf_pspotri = dlaf_pcpotri = dlaf_pzpotri = pXpotri
@@ -421,3 +492,6 @@ dlaf_pdlange = dlaf_pslange = dlaf_pclange = dlaf_pzlange = pXlange
 dlaf_pdlansy = dlaf_pslansy = pXlansy
 dlaf_pclanhe = dlaf_pzlanhe = pXlanhe
 dlaf_pdlantr = dlaf_pslantr = dlaf_pclantr = dlaf_pzlantr = pXlantr
+dlaf_pdpocon = dlaf_pspocon = dlaf_pcpocon = dlaf_pzpocon = pXpocon
+dlaf_pdtrcon = dlaf_pstrcon = dlaf_pctrcon = dlaf_pztrcon = pXtrcon
+dlaf_pdpotrs = dlaf_pspotrs = dlaf_pcpotrs = dlaf_pzpotrs = pXpotrs

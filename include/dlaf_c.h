@@ -141,6 +141,27 @@ double dlaf_pzlanhe(char norm, char uplo, int n, const dlaf_complex_z* a,
 double dlaf_pdlantr(char norm, char uplo, char diag, int m, int n,
                     const double* a, int ia, int ja, const int desca[9]);
 
+/* Condition estimates and the Cholesky solve (ScaLAPACK p?pocon / p?trcon /
+ * p?potrs without the workspace arguments); a is only read, ia = ja = 1.
+ * pocon: a holds the Cholesky factor left by p?potrf in its uplo triangle,
+ * anorm is the one-norm of the matrix before it was factored (p?lansy /
+ * p?lanhe); trcon: norm '1' / 'O' or 'I'. *rcond is the estimated reciprocal
+ * condition number (0 for a singular matrix, 1 for n = 0). potrs overwrites b
+ * (n x nrhs) with the solution of A X = B. *info = 0 on success. */
+void dlaf_pdpocon(char uplo, int n, const double* a, int ia, int ja,
+                  const int desca[9], double anorm, double* rcond, int* info);
+void dlaf_pzpocon(char uplo, int n, const dlaf_complex_z* a, int ia, int ja,
+                  const int desca[9], double anorm, double* rcond, int* info);
+void dlaf_pdtrcon(char norm, char uplo, char diag, int n, const double* a,
+                  int ia, int ja, const int desca[9], double* rcond,
+                  int* info);
+void dlaf_pztrcon(char norm, char uplo, char diag, int n,
+                  const dlaf_complex_z* a, int ia, int ja, const int desca[9],
+                  double* rcond, int* info);
+void dlaf_pdpotrs(char uplo, int n, int nrhs, const double* a, int ia, int ja,
+                  const int desca[9], double* b, int ib, int jb,
+                  const int descb[9], int* info);
+
 #ifdef __cplusplus
 }
 #endif

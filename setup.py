@@ -28,6 +28,7 @@ setup(
                 "csrc/bisect.hip",
                 "csrc/invit.hip",
                 "csrc/norms.hip",
+                "csrc/trsv.hip",
                 "csrc/rocblas_batch.cpp",
                 "csrc/chase_gpu.hip",
             ],
