@@ -226,6 +226,60 @@ int run_potrs(int ctx, char uplo, int n, int nrhs, const void* a,
   }
 }
 
+// the leading m x n part of a descriptor
+struct DLAF_descriptor leading(struct DLAF_descriptor d, int m, int n) {
+  d.m = m;
+  d.n = n;
+  return d;
+}
+
+int run_porfs(int ctx, char uplo, int n, int nrhs, const void* a,
+              const struct DLAF_descriptor& da, const void* af,
+              const struct DLAF_descriptor& daf, const void* b,
+              const struct DLAF_descriptor& db, void* x,
+              const struct DLAF_descriptor& dx, double* ferr, double* berr,
+              const char* dtype) {
+  Gil g;
+  try {
+    auto av = np_view(ctx, const_cast<void*>(a), da, dtype);
+    auto fv = np_view(ctx, const_cast<void*>(af), daf, dtype);
+    auto bv = np_view(ctx, const_cast<void*>(b), db, dtype);
+    auto xv = np_view(ctx, x, dx, dtype);
+    return capi_->attr("dlaf_cholesky_refine")(
+        ctx, std::string(1, uplo), av, desc_obj(leading(da, n, n)), fv,
+        desc_obj(leading(daf, n, n)), bv, desc_obj(leading(db, n, nrhs)), xv,
+        desc_obj(leading(dx, n, nrhs)), np_vec(ferr, nrhs, "float64"),
+        np_vec(berr, nrhs, "float64")).cast<int>();
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: cholesky refine failed: %s\n", e.what());
+    return -1;
+  }
+}
+
+int run_sposv(int ctx, char uplo, int n, int nrhs, const void* a,
+              const struct DLAF_descriptor& da, const void* b,
+              const struct DLAF_descriptor& db, void* x,
+              const struct DLAF_descriptor& dx, int* iter,
+              const char* dtype) {
+  Gil g;
+  try {
+    auto av = np_view(ctx, const_cast<void*>(a), da, dtype);
+    auto bv = np_view(ctx, const_cast<void*>(b), db, dtype);
+    auto xv = np_view(ctx, x, dx, dtype);
+    auto out = capi_->attr("dlaf_cholesky_solve_mixed")(
+        ctx, std::string(1, uplo), av, desc_obj(leading(da, n, n)), bv,
+        desc_obj(leading(db, n, nrhs)), xv, desc_obj(leading(dx, n, nrhs)))
+        .cast<py::tuple>();
+    *iter = out[0].cast<int>();
+    return out[1].cast<int>();
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: mixed cholesky solve failed: %s\n",
+                 e.what());
+    *iter = 0;
+    return -1;
+  }
+}
+
 struct DLAF_descriptor from_sl(int n, const int d[9], int m = -1) {
   struct DLAF_descriptor out;
   out.m = m >= 0 ? m : d[2];
@@ -512,5 +566,35 @@ void dlaf_pdpotrs(char uplo, int n, int nrhs, const double* a, int ia, int ja,
   *info = run_potrs(sl_grid(), uplo, n, nrhs, a, from_sl(n, desca), b,
                     from_sl(nrhs, descb), "float64");
 }
+
+#define DLAF_PORFS(name, T, dtype)                                            \
+  void name(char uplo, int n, int nrhs, const T* a, int ia, int ja,           \
+            const int desca[9], const T* af, int iaf, int jaf,                \
+            const int descaf[9], const T* b, int ib, int jb,                  \
+            const int descb[9], T* x, int ix, int jx, const int descx[9],     \
+            double* ferr, double* berr, int* info) {                          \
+    (void)ia; (void)ja; (void)iaf; (void)jaf;                                 \
+    (void)ib; (void)jb; (void)ix; (void)jx;                                   \
+    *info = run_porfs(sl_grid(), uplo, n, nrhs, a, from_sl(n, desca), af,     \
+                      from_sl(n, descaf), b, from_sl(nrhs, descb), x,         \
+                      from_sl(nrhs, descx), ferr, berr, dtype);               \
+  }
+DLAF_PORFS(dlaf_pdporfs, double, "float64")
+DLAF_PORFS(dlaf_pzporfs, dlaf_complex_z, "complex128")
+#undef DLAF_PORFS
+
+#define DLAF_SPOSV(name, T, dtype)                                            \
+  void name(char uplo, int n, int nrhs, const T* a, int ia, int ja,           \
+            const int desca[9], const T* b, int ib, int jb,                   \
+            const int descb[9], T* x, int ix, int jx, const int descx[9],     \
+            int* iter, int* info) {                                           \
+    (void)ia; (void)ja; (void)ib; (void)jb; (void)ix; (void)jx;               \
+    *info = run_sposv(sl_grid(), uplo, n, nrhs, a, from_sl(n, desca), b,      \
+                      from_sl(nrhs, descb), x, from_sl(nrhs, descx), iter,    \
+                      dtype);                                                 \
+  }
+DLAF_SPOSV(dlaf_pdsposv, double, "float64")
+DLAF_SPOSV(dlaf_pzcposv, dlaf_complex_z, "complex128")
+#undef DLAF_SPOSV
 
 }  // extern "C"

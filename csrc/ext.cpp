@@ -548,6 +548,54 @@ void trsv_tiles(torch::Tensor storage, torch::Tensor dinv, torch::Tensor x,
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- Hermitian matrix-vector product over the tile storage (hemv.hip) ----
+
+// y = A x and, unless yabs is empty, yabs = |A| |x|; storage [nt, nt, nb, nb]
+// holds the Hermitian A in its uplo triangle, x / y / yabs are [nt * nb]
+// (yabs of the real dtype). Entries at or beyond n are left as they are.
+void hemv_tiles(torch::Tensor storage, torch::Tensor x, torch::Tensor y,
+                torch::Tensor yabs, int64_t n, int64_t uplo) {
+  TORCH_CHECK(storage.is_cuda() && storage.dim() == 4 &&
+              storage.is_contiguous() && storage.size(0) == storage.size(1) &&
+              storage.size(2) == storage.size(3),
+              "storage must be a contiguous [nt, nt, nb, nb] device tensor");
+  const int64_t nt = storage.size(0), nb = storage.size(2);
+  const int64_t strips =
+      (nb + dlaf::kHemvStripRows - 1) / dlaf::kHemvStripRows;
+  TORCH_CHECK(nb > 0 && nt * nb < (1LL << 31) && nt * nt < (1LL << 20) &&
+              nt * (nt + 1) / 2 * strips < (1LL << 31),
+              "matrix too large for the product kernel");
+  TORCH_CHECK(n >= 0 && n <= nt * nb && n > (nt - 1) * nb,
+              "n does not match the storage");
+  for (const torch::Tensor* v : {&x, &y})
+    TORCH_CHECK(v->dim() == 1 && v->is_contiguous() && v->size(0) == nt * nb &&
+                v->scalar_type() == storage.scalar_type() &&
+                v->device() == storage.device(),
+                "x and y must be contiguous [nt * nb] like the storage");
+  TORCH_CHECK(x.data_ptr() != y.data_ptr() || nt == 0,
+              "x and y must not alias");
+  const bool want_abs = yabs.numel() > 0;
+  if (want_abs)
+    TORCH_CHECK(yabs.dim() == 1 && yabs.is_contiguous() &&
+                yabs.size(0) == nt * nb &&
+                yabs.scalar_type() == c10::toRealValueType(storage.scalar_type()) &&
+                yabs.device() == storage.device(),
+                "yabs must be empty or contiguous [nt * nb] of the real dtype");
+  TORCH_CHECK(uplo == 0 || uplo == 1, "bad uplo");
+  if (nt == 0) return;
+  auto work = torch::empty({dlaf::hemv_work_size((int)nt, (int)nb)},
+                           storage.options().dtype(torch::kFloat64));
+  dispatch_dtype(storage.scalar_type(), [&](auto tag) {
+    using S = typename decltype(tag)::type;
+    using R = typename decltype(tag)::real_t;
+    dlaf::hemv_tiles(ptr<const S>(storage), ptr<const S>(x), ptr<S>(y),
+                     want_abs ? yabs.data_ptr<R>() : (R*)nullptr, (int)nt,
+                     (int)nb, n, (int)uplo, work.data_ptr<double>(),
+                     cur_stream());
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
 
 // csrc/band_chase.cpp
@@ -581,6 +629,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "diagonal tiles applied through their inverses",
         py::arg("storage"), py::arg("dinv"), py::arg("x"), py::arg("n"),
         py::arg("uplo"), py::arg("op"));
+  m.def("hemv_tiles", &hemv_tiles,
+        "y = A x (and yabs = |A| |x| unless yabs is empty) for one vector, A "
+        "Hermitian in the uplo triangle of a local tile storage, read once",
+        py::arg("storage"), py::arg("x"), py::arg("y"), py::arg("yabs"),
+        py::arg("n"), py::arg("uplo"));
+  m.def("hemv_work_size", &dlaf::hemv_work_size,
+        "doubles of workspace hemv_tiles uses", py::arg("nt"), py::arg("nb"));
   m.def("sturm_interval", &sturm_interval,
         "(gl, gu, pivmin): widened Gershgorin interval and pivot floor");
   m.def("dc_deflate_scan", &dc_deflate_scan,

@@ -169,4 +169,20 @@ template <typename S>
 void trsv_tiles(const S* a, const S* dinv, S* x, S* work, int nt, int nb,
                 int64_t n, int uplo, int op, hipStream_t stream);
 
+// ---- Hermitian matrix-vector product over the tile storage, csrc/hemv.hip
+// y = A x and, when yabs is not null, yabs = |A| |x| (CABS1) from the same
+// pass; A is the Hermitian matrix whose uplo (0 Lower, 1 Upper) triangle is
+// in the local [nt, nt, nb, nb] storage a, x / y / yabs hold nt * nb
+// elements. Every stored element of the triangle is read once; the other
+// triangle, the imaginary part of the diagonal and rows and columns at or
+// beyond n are never read into a sum, and y / yabs are not written at or
+// beyond n. work holds hemv_work_size() doubles and needs no clearing. Two
+// plain launches on the stream; nt <= 0 or n <= 0 launches nothing.
+constexpr int kHemvStripRows = 64;
+int64_t hemv_work_size(int nt, int nb);
+template <typename S>
+void hemv_tiles(const S* a, const S* x, S* y,
+                typename ScalarTraits<S>::real_t* yabs, int nt, int nb,
+                int64_t n, int uplo, double* work, hipStream_t stream);
+
 }  // namespace dlaf

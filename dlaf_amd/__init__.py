@@ -23,7 +23,9 @@ Public API (mirrors the reference's free-function API):
     hermitian_generalized_eigenvalues, and the partial-spectrum eigenvector
     solvers tridiagonal_eigenvectors, tridiagonal_eigensolver_bisect, and the
     condition estimates triangular_rcond, cholesky_rcond (with
-    TriangularVectorSolver, inverse_norm_estimate) and cholesky_solve
+    TriangularVectorSolver, inverse_norm_estimate) and cholesky_solve, and the
+    refinement layer cholesky_refine, cholesky_solve_expert,
+    cholesky_solve_mixed (with HermitianVectorProduct, cholesky_info)
 """
 
 from .types import Side, UpLo, Op, Diag  # noqa: F401
@@ -47,6 +49,13 @@ from .algs.condition import (  # noqa: F401
     triangular_rcond,
     cholesky_rcond,
     cholesky_solve,
+)
+from .algs.refine import (  # noqa: F401
+    HermitianVectorProduct,
+    cholesky_info,
+    cholesky_refine,
+    cholesky_solve_expert,
+    cholesky_solve_mixed,
 )
 from .algs.eigensolver import (  # noqa: F401
     hermitian_eigensolver,

@@ -4,7 +4,8 @@ Counterpart of the reference's C API (``include/dlaf_c/*``, ``src/c_api/*``):
 grid management by integer context, ScaLAPACK-style descriptors, and
 ``p?potrf / p?potri / p?trtri / p?syevd / p?heevd / p?sygvd / p?hegvd``
 entry points, the norms ``p?lange / p?lansy / p?lanhe / p?lantr``, the
-condition estimates ``p?pocon / p?trcon`` and the solve ``p?potrs``, all
+condition estimates ``p?pocon / p?trcon``, the solve ``p?potrs``, its
+refinement ``p?porfs`` and the mixed-precision solves ``pdsposv / pzcposv``, all
 operating on the caller's LOCAL block-cyclic column-major buffer (numpy or
 torch). Each call wraps the buffer into a tiled ``Matrix``
 (mirrored to the GPU when available), runs the native algorithm, and copies
@@ -35,6 +36,7 @@ from .algs.tridiag_bisect import (hermitian_eigenvalues,
                                   hermitian_generalized_eigenvalues)
 from .algs.norm import matrix_norm
 from .algs.condition import cholesky_rcond, triangular_rcond, cholesky_solve
+from .algs.refine import cholesky_info, cholesky_refine, cholesky_solve_mixed
 
 
 @dataclass
@@ -147,34 +149,9 @@ def _unwrap_local(mat: Matrix, a_local) -> None:
 
 
 def _potrf_info(mat: Matrix, grid=None) -> int:
-    """info > 0 when the input was not positive definite: a failed pivot
-    sqrt produces NaN on that diagonal (reference counterpart: the
-    cusolver-info device assert, ``src/cusolver/assert_info.cu:35``; here
-    the check is an O(n) diagonal scan returned as ScaLAPACK-style info).
-
-    Distributed grids: each rank scans only its owned diagonal tiles, then
-    the smallest positive info is all-reduced over the full grid so EVERY
-    rank returns the same global info (ScaLAPACK semantics — the reference
-    returns a consistent info on all ranks)."""
-    info = 0
-    nt = mat.dist.nr_tiles[0]
-    for k in range(nt):
-        if mat.dist.rank_of_tile((k, k)) != (mat.dist.rank_row, mat.dist.rank_col):
-            continue
-        d = mat.tile((k, k)).diagonal()
-        bad = torch.isnan(d.real if d.is_complex() else d)
-        if bool(bad.any()):
-            info = k * mat.dist.mb + int(bad.int().argmax()) + 1
-            break
-    if grid is not None and grid.distributed:
-        import torch.distributed as tdist
-        # min over positive infos == first failing pivot; encode 0 as +inf
-        t = torch.tensor([float(info) if info > 0 else float("inf")],
-                         dtype=torch.float64)
-        tdist.all_reduce(t, op=tdist.ReduceOp.MIN, group=grid.full_group)
-        v = float(t.item())
-        info = 0 if v == float("inf") else int(v)
-    return info
+    """info > 0 when the input was not positive definite: the failed-pivot
+    scan of ``algs.refine.cholesky_info``, the same on every rank."""
+    return cholesky_info(mat, grid)
 
 
 def dlaf_cholesky_factorization(ctx: int, uplo: str, a_local, desc: DLAF_descriptor) -> int:
@@ -390,6 +367,47 @@ def dlaf_cholesky_solve(ctx: int, uplo: str, a_local, desca: DLAF_descriptor,
     return 0
 
 
+def dlaf_cholesky_refine(ctx: int, uplo: str, a_local, desca: DLAF_descriptor,
+                         af_local, descaf: DLAF_descriptor, b_local,
+                         descb: DLAF_descriptor, x_local,
+                         descx: DLAF_descriptor, ferr_out, berr_out) -> int:
+    """Refine the solution in ``x_local`` of A X = B and store the forward
+    error bounds and backward errors (``cholesky_refine``) in ``ferr_out`` /
+    ``berr_out`` ([nrhs] real buffers). ``a_local`` holds A, ``af_local`` its
+    Cholesky factor, ``b_local`` B; the three are only read."""
+    grid = _grid(ctx)
+    dev = _device_for(grid)
+    g = grid if grid.distributed else None
+    mat = _wrap_local(a_local, desca, grid, dev)
+    fac = _wrap_local(af_local, descaf, grid, dev)
+    rhs = _wrap_local(b_local, descb, grid, dev)
+    sol = _wrap_local(x_local, descx, grid, dev)
+    ferr, berr = cholesky_refine(_uplo(uplo), mat, fac, rhs, sol, g)
+    _store_w(ferr, ferr_out)
+    _store_w(berr, berr_out)
+    _unwrap_local(sol, x_local)
+    return 0
+
+
+def dlaf_cholesky_solve_mixed(ctx: int, uplo: str, a_local,
+                              desca: DLAF_descriptor, b_local,
+                              descb: DLAF_descriptor, x_local,
+                              descx: DLAF_descriptor):
+    """Solve A X = B (float64 / complex128) with a single precision
+    factorization and double precision refinement (``cholesky_solve_mixed``);
+    ``x_local`` receives X. Returns ``(iters, info)``. ``a_local`` and
+    ``b_local`` are only read: the factor is not left in ``a_local``."""
+    grid = _grid(ctx)
+    dev = _device_for(grid)
+    mat = _wrap_local(a_local, desca, grid, dev)
+    rhs = _wrap_local(b_local, descb, grid, dev)
+    sol, iters, info = cholesky_solve_mixed(
+        _uplo(uplo), mat, rhs, grid if grid.distributed else None)
+    if sol is not None:
+        _unwrap_local(sol, x_local)
+    return iters, info
+
+
 # ---- ScaLAPACK-style shims (reference dlaf_c/...: dlaf_p{s,d,c,z}potrf etc.) ----
 
 def _sl_desc(n, mb, nb, uplo_n=None, m=None) -> DLAF_descriptor:
@@ -480,6 +498,33 @@ def pXpotrs(ctx: int, uplo: str, n: int, nrhs: int, a_local, ia: int, ja: int,
                                b_local, _norm_desc(descb, n, nrhs))
 
 
+def pXporfs(ctx: int, uplo: str, n: int, nrhs: int, a_local, ia: int, ja: int,
+            desca: DLAF_descriptor, af_local, iaf: int, jaf: int,
+            descaf: DLAF_descriptor, b_local, ib: int, jb: int,
+            descb: DLAF_descriptor, x_local, ix: int, jx: int,
+            descx: DLAF_descriptor, ferr_out, berr_out) -> int:
+    """p?porfs (its workspace arguments have no counterpart)."""
+    assert (ia, ja) == (1, 1) and (iaf, jaf) == (1, 1)
+    assert (ib, jb) == (1, 1) and (ix, jx) == (1, 1)
+    return dlaf_cholesky_refine(ctx, uplo, a_local, _norm_desc(desca, n, n),
+                                af_local, _norm_desc(descaf, n, n), b_local,
+                                _norm_desc(descb, n, nrhs), x_local,
+                                _norm_desc(descx, n, nrhs), ferr_out,
+                                berr_out)
+
+
+def pXsposv(ctx: int, uplo: str, n: int, nrhs: int, a_local, ia: int, ja: int,
+            desca: DLAF_descriptor, b_local, ib: int, jb: int,
+            descb: DLAF_descriptor, x_local, ix: int, jx: int,
+            descx: DLAF_descriptor):
+    """dsposv / zcposv over block-cyclic buffers; returns (iter, info)."""
+    assert (ia, ja) == (1, 1) and (ib, jb) == (1, 1) and (ix, jx) == (1, 1)
+    return dlaf_cholesky_solve_mixed(ctx, uplo, a_local,
+                                     _norm_desc(desca, n, n), b_local,
+                                     _norm_desc(descb, n, nrhs), x_local,
+                                     _norm_desc(descx, n, nrhs))
+
+
 # dtype-suffixed aliases matching the reference's C symbol names
 dlaf_pdpotrf = dlaf_pspotrf = dlaf_pcpotrf = dlaf_pzpotrf = pXpotrf
 dlaf_pdpotri = dlaf_pspotri = dlaf_pcpotri = dlaf_pzpotri = pXpotri
@@ -495,3 +540,5 @@ dlaf_pdlantr = dlaf_pslantr = dlaf_pclantr = dlaf_pzlantr = pXlantr
 dlaf_pdpocon = dlaf_pspocon = dlaf_pcpocon = dlaf_pzpocon = pXpocon
 dlaf_pdtrcon = dlaf_pstrcon = dlaf_pctrcon = dlaf_pztrcon = pXtrcon
 dlaf_pdpotrs = dlaf_pspotrs = dlaf_pcpotrs = dlaf_pzpotrs = pXpotrs
+dlaf_pdporfs = dlaf_psporfs = dlaf_pcporfs = dlaf_pzporfs = pXporfs
+dlaf_pdsposv = dlaf_pzcposv = pXsposv

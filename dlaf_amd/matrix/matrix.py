@@ -175,6 +175,12 @@ class Matrix:
     def clone(self) -> "Matrix":
         return Matrix(self.dist, self.dtype, self.device, self.grid, _storage=self.storage.clone())
 
+    def astype(self, dtype: torch.dtype) -> "Matrix":
+        """A copy in another dtype with the same distribution; the identity
+        padding of partial edge tiles converts exactly."""
+        return Matrix(self.dist, dtype, self.device, self.grid,
+                      _storage=self.storage.to(dtype, copy=True))
+
     def __repr__(self) -> str:
         d = self.dist
         return (

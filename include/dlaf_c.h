@@ -162,6 +162,40 @@ void dlaf_pdpotrs(char uplo, int n, int nrhs, const double* a, int ia, int ja,
                   const int desca[9], double* b, int ib, int jb,
                   const int descb[9], int* info);
 
+/* Refinement and the mixed-precision solve (p?porfs without the workspace
+ * arguments; dsposv / zcposv over block-cyclic buffers); every i / j = 1.
+ * porfs: a holds the Hermitian positive definite matrix, af its Cholesky
+ * factor as left by p?potrf, b the right-hand sides (all three only read);
+ * x (n x nrhs), a solution as p?potrs returns it, is refined in place.
+ * ferr[nrhs] receives estimated bounds on the relative forward error of each
+ * column, berr[nrhs] the componentwise relative backward errors.
+ * sposv: factors in single precision and refines in double; x receives the
+ * solution, a and b are only read (unlike LAPACK, no factor is left in a).
+ * *iter >= 0 is the number of refinement steps; < 0 means that the solution
+ * comes from a double precision factorization: -2 an entry overflows single
+ * precision, -3 the single precision factorization failed, -31 no
+ * convergence in 30 steps. *info = 0 on success, > 0 the order of the
+ * leading minor that is not positive definite. */
+void dlaf_pdporfs(char uplo, int n, int nrhs, const double* a, int ia, int ja,
+                  const int desca[9], const double* af, int iaf, int jaf,
+                  const int descaf[9], const double* b, int ib, int jb,
+                  const int descb[9], double* x, int ix, int jx,
+                  const int descx[9], double* ferr, double* berr, int* info);
+void dlaf_pzporfs(char uplo, int n, int nrhs, const dlaf_complex_z* a, int ia,
+                  int ja, const int desca[9], const dlaf_complex_z* af,
+                  int iaf, int jaf, const int descaf[9],
+                  const dlaf_complex_z* b, int ib, int jb, const int descb[9],
+                  dlaf_complex_z* x, int ix, int jx, const int descx[9],
+                  double* ferr, double* berr, int* info);
+void dlaf_pdsposv(char uplo, int n, int nrhs, const double* a, int ia, int ja,
+                  const int desca[9], const double* b, int ib, int jb,
+                  const int descb[9], double* x, int ix, int jx,
+                  const int descx[9], int* iter, int* info);
+void dlaf_pzcposv(char uplo, int n, int nrhs, const dlaf_complex_z* a, int ia,
+                  int ja, const int desca[9], const dlaf_complex_z* b, int ib,
+                  int jb, const int descb[9], dlaf_complex_z* x, int ix,
+                  int jx, const int descx[9], int* iter, int* info);
+
 #ifdef __cplusplus
 }
 #endif

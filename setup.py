@@ -29,6 +29,7 @@ setup(
                 "csrc/invit.hip",
                 "csrc/norms.hip",
                 "csrc/trsv.hip",
+                "csrc/hemv.hip",
                 "csrc/rocblas_batch.cpp",
                 "csrc/chase_gpu.hip",
             ],

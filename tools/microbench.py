@@ -1,5 +1,11 @@
 #!/usr/bin/env python3
-"""Kernel microbenchmarks on one MI355X: fused GEMM TF/s, potrf/trtri latency."""
+"""Kernel microbenchmarks on one MI355X: fused GEMM TF/s, potrf/trtri latency.
+
+``--hemv [n nb]``: the Hermitian vector-product kernel against the floor of
+reading the stored triangle once at 6.3 TB/s and against
+``hermitian_multiplication`` on n x nrhs (the per-column crossover).
+``--mixed [n nb]``: ``cholesky_solve_mixed`` against the float64
+factorization and solve. Either runs alone, without the default list."""
 
 import os
 import sys
@@ -152,8 +158,118 @@ def bench_lib_batched(dtype=torch.float64, nb=512, nt=63, iters=5):
         print(f"trailing {tag} {dtype} nb={nb} tiles={ntc}: {dt_s*1e3:.2f} ms  "
               f"{fl/dt_s/1e12:.2f} TFLOP/s", flush=True)
 
+def _median_ms(fn, reps=7, warm=2, before=None):
+    import statistics
+    ts = []
+    for i in range(warm + reps):
+        if before:
+            before()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        if i >= warm:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts), min(ts)
+
+
+def _spd(n, nb, dtype):
+    from dlaf_amd import Matrix
+    from dlaf_amd.matrix import util as mutil
+    mat = Matrix.create(n, n, nb, nb, dtype=dtype, device="cuda")
+    mutil.set_random_hermitian_positive_definite(mat, seed=1)
+    return mat
+
+
+def bench_hemv(dtype=torch.float64, n=32768, nb=512, nrhs_list=(1, 2, 4, 8, 16, 32)):
+    """hemv_tiles (y alone, and with |A||x|) against the read floor of the
+    stored triangle, and against hermitian_multiplication on n x nrhs."""
+    from dlaf_amd import (Matrix, Side, UpLo, HermitianVectorProduct,
+                          hermitian_multiplication)
+    from dlaf_amd.ops._ext import get_ext
+    A = _spd(n, nb, dtype)
+    esz = A.storage.element_size()
+    nt = A.dist.nr_tiles[0]
+    floor = n * (n + 1) / 2 * esz / 6.3e12 * 1e3
+    work = get_ext().hemv_work_size(nt, nb) * 8
+    hv = HermitianVectorProduct(UpLo.Lower, A, method="kernel")
+    x = torch.randn(n, dtype=dtype, device="cuda")
+    print(f"hemv {dtype} n={n} nb={nb}: triangle {n * (n + 1) / 2 * esz / 2**30:.2f} GiB, "
+          f"read floor {floor:.3f} ms, workspace {work / 2**20:.1f} MiB", flush=True)
+    for want_abs in (False, True):
+        med, mn = _median_ms(lambda: hv.apply(x, want_abs=want_abs), reps=15)
+        print(f"  hemv kernel abs={int(want_abs)}: median {med:.3f} ms  min {mn:.3f} ms  "
+              f"{med / floor:.2f} x floor  {n * (n + 1) / 2 * esz / med / 1e6:.0f} GB/s",
+              flush=True)
+    for nrhs in nrhs_list:
+        X = Matrix.create(n, nrhs, nb, nb, dtype=dtype, device="cuda")
+        X.storage.normal_()
+        Y = X.like()
+        hemm, _ = _median_ms(lambda: hermitian_multiplication(
+            Side.Left, UpLo.Lower, 1.0, A, X, 0.0, Y), reps=5, warm=1)
+        cols, _ = _median_ms(lambda: [hv.apply(x) for _ in range(nrhs)], reps=5, warm=1)
+        print(f"  nrhs={nrhs:3d}: hermitian_multiplication {hemm:9.3f} ms   "
+              f"kernel per column {cols:9.3f} ms", flush=True)
+
+
+def bench_mixed_solve(dtype=torch.float64, n=16384, nb=512, nrhs=4):
+    """cholesky_solve_mixed against cholesky_factorization + cholesky_solve
+    in the same precision as the input, and the two factorizations alone."""
+    from dlaf_amd import (Matrix, UpLo, cholesky_factorization, cholesky_solve,
+                          cholesky_solve_mixed)
+    A = _spd(n, nb, dtype)
+    B = Matrix.create(n, nrhs, nb, nb, dtype=dtype, device="cuda")
+    B.set_from_global(torch.randn(n, nrhs, dtype=dtype, device="cuda"))
+    low = torch.float32 if dtype == torch.float64 else torch.complex64
+    out = {}
+
+    def plain():
+        L = A.clone()
+        cholesky_factorization(UpLo.Lower, L)
+        X = B.clone()
+        cholesky_solve(UpLo.Lower, L, X)
+
+    def mixed():
+        out["r"] = cholesky_solve_mixed(UpLo.Lower, A, B)
+
+    Ls = A.astype(low)
+    keep_s, keep_d = Ls.storage.clone(), A.storage.clone()
+    L = A.clone()
+    f_lo, _ = _median_ms(lambda: cholesky_factorization(UpLo.Lower, Ls), reps=3, warm=1,
+                         before=lambda: Ls.storage.copy_(keep_s))
+    f_hi, _ = _median_ms(lambda: cholesky_factorization(UpLo.Lower, L), reps=3, warm=1,
+                         before=lambda: L.storage.copy_(keep_d))
+    del Ls, L, keep_s, keep_d
+    t_plain, _ = _median_ms(plain, reps=3, warm=1)
+    t_mixed, _ = _median_ms(mixed, reps=3, warm=1)
+    print(f"mixed solve {dtype} n={n} nb={nb} nrhs={nrhs}: factorization {low} {f_lo:.1f} ms, "
+          f"{dtype} {f_hi:.1f} ms ({f_hi / f_lo:.2f} x); potrf+potrs {t_plain:.1f} ms, "
+          f"cholesky_solve_mixed {t_mixed:.1f} ms ({t_plain / t_mixed:.2f} x), "
+          f"iters={out['r'][1]} info={out['r'][2]}", flush=True)
+
+
+def _shape_args(flag, n, nb):
+    rest = sys.argv[sys.argv.index(flag) + 1:]
+    nums = []
+    for a in rest:
+        if not a.isdigit():
+            break
+        nums.append(int(a))
+    return (nums + [n, nb][len(nums):])[:2]
+
+
 if __name__ == "__main__":
     print(torch.cuda.get_device_name(0))
+    if "--hemv" in sys.argv or "--mixed" in sys.argv:
+        if "--hemv" in sys.argv:
+            n, nb = _shape_args("--hemv", 32768, 512)
+            bench_hemv(torch.float64, n, nb)
+            bench_hemv(torch.complex128, n // 2, nb)
+        if "--mixed" in sys.argv:
+            n, nb = _shape_args("--mixed", 16384, 512)
+            bench_mixed_solve(torch.float64, n, nb, nrhs=4)    # vector kernels
+            bench_mixed_solve(torch.float64, n, nb, nrhs=64)   # tiled HEMM / TRSM
+        sys.exit(0)
     bench_gemm(torch.float64, 512, 128)
     bench_gemm(torch.float64, 512, 1024, iters=5)
     bench_gemm(torch.float32, 512, 128)
