@@ -2,10 +2,8 @@
 //
 // All entry points take CUDA (ROCm) tensors, run on the CURRENT torch stream
 // (so the Python runtime's stream/event scheduling applies), and are
-// asynchronous. The per-tile Cholesky (`potrf_tile`) is host-orchestrated here
-// in C++: potrf_invert_block (single-WG LDS kernel: factor + block inverse) +
-// fused-GEMM panel/trailing updates, with all GemmDescs prebuilt on the device
-// by the Python layer.
+// asynchronous. The per-tile Cholesky (`potrf_tile`) is one launch per block
+// column of the tile (csrc/factor.hip, csrc/potrf_plan.h).
 //
 // Every binding goes through dispatch_dtype: scalar type -> element-type tag
 // -> generic lambda calling the typed entry points of kernels.h.
@@ -24,6 +22,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "potrf_plan.h"
 #include "sturm.h"
 #include "tridiag_lu.h"
 
@@ -143,43 +142,25 @@ void trtri_lower(torch::Tensor L, torch::Tensor T, int64_t n, int64_t ldl,
 // In-place Cholesky (Lower) of the leading n x n of a tile with row stride ld.
 // Also fills `dinv` ([nblocks, bsz, bsz] contiguous) with the inverses of the
 // bsz x bsz diagonal blocks of the factor — the panel TRSM then becomes GEMMs.
-// `ddesc` is the prebuilt device descriptor table ([2*nblocks, 6] int64,
-// cached by the Python layer per (n, ld, dtype)): rows 2d   = panel desc
-// (A21 offsets), rows 2d+1 = trailing desc, exactly as _potrf_descs builds.
+// `side` is the workspace of dlaf::potrf_tile_fused (cached by the Python
+// layer); calls that may run concurrently need separate ones.
 void potrf_tile(torch::Tensor A, int64_t n, int64_t ld, torch::Tensor dinv,
-                torch::Tensor ddesc) {
+                torch::Tensor side) {
   TORCH_CHECK(A.is_cuda() && dinv.is_cuda() && dinv.is_contiguous());
+  TORCH_CHECK(side.is_cuda() && side.is_contiguous());
+  TORCH_CHECK(dinv.scalar_type() == A.scalar_type() &&
+              side.scalar_type() == A.scalar_type(), "dtype mismatch");
+  TORCH_CHECK(n >= 0 && n < (int64_t(1) << 30) && ld >= n, "bad n / ld");
   constexpr int bsz = kPotrfBsz;
-  const int nblocks = (int)((n + bsz - 1) / bsz);
+  const int nblocks = dlaf::potrf_plan::nblocks((int)n, bsz);
   TORCH_CHECK(dinv.numel() >= (int64_t)nblocks * bsz * bsz, "dinv too small");
-  TORCH_CHECK(ddesc.is_cuda() && ddesc.scalar_type() == at::kLong &&
-              ddesc.is_contiguous() && ddesc.numel() >= nblocks * 12,
-              "bad ddesc");
+  TORCH_CHECK(side.numel() >= dlaf::potrf_plan::side_elems(nblocks, bsz),
+              "side workspace too small");
   auto s = cur_stream();
-  auto descs = reinterpret_cast<const GemmDesc*>(ddesc.data_ptr<int64_t>());
-
   dispatch_dtype(A.scalar_type(), [&](auto tag) {
     using S = typename decltype(tag)::type;
-    // OP_C == OP_T for real S
-    const S one = scalar<S>(1, 0), zero = scalar<S>(0, 0);
-    const S minus_one = scalar<S>(-1, 0);
-    S* Ap = ptr<S>(A);
-    for (int d = 0; d < nblocks; ++d) {
-      const int64_t c0 = (int64_t)d * bsz;
-      const int bs = (int)std::min<int64_t>(bsz, n - c0);
-      S* Dp = ptr<S>(dinv) + (int64_t)d * bsz * bsz;
-      // 1+2) fused: factor diagonal block and write its inverse -> dinv[d]
-      dlaf::potrf_invert_block(Ap + c0 * ld + c0, bs, ld, Dp, 1, s);
-      const int64_t rows_below = n - c0 - bs;
-      if (rows_below <= 0) continue;
-      const GemmDesc* dp = descs + 2 * d;
-      // 3) panel: X = A21 * dinv^H  (in place)
-      dlaf::gemm_tiles(dp, 1, Ap, Dp, Ap, rows_below, bs, bs, ld, bsz, ld, OP_N,
-                       OP_C, one, zero, s, 1);
-      // 4) trailing: A22 -= X X^H
-      dlaf::gemm_tiles(dp + 1, 1, Ap, Ap, Ap, rows_below, rows_below, bs, ld,
-                       ld, ld, OP_N, OP_C, minus_one, one, s, 0);
-    }
+    dlaf::potrf_tile_fused(ptr<S>(A), (int)n, (int)ld, ptr<S>(dinv),
+                           ptr<S>(side), s);
   });
   HIP_CHECK(hipGetLastError());
 }

@@ -1,15 +1,21 @@
 // Single-tile factorization building blocks for CDNA4.
 //
 // * potrf_invert_block: single-workgroup LDS-resident Cholesky of one diagonal
-//   block fused with its inversion. The tile Cholesky of an nb x nb tile is
-//   orchestrated on the host (ext.cpp) as potrf_invert_block + fused GEMM
-//   panel/trailing updates against the block inverse — the per-tile analog of
-//   the right-looking algorithm, replacing the reference's rocSOLVER potrf
-//   call.
+//   block fused with its inversion.
+// * potrf_tile_fused: the tile Cholesky of an nb x nb tile, right-looking over
+//   64-column blocks, one launch per block column: every workgroup of launch d
+//   recomputes the two panel blocks it needs against dinv[d-1] and updates its
+//   own trailing block, and the diagonal workgroup goes on to factor and
+//   invert it (csrc/potrf_plan.h has the decomposition and the ownership of
+//   every write). Replaces the reference's rocSOLVER potrf call (SURVEY.md
+//   §2.4).
 // * trtri_lower: column-parallel lower-triangular inverse (thread-per-column
 //   forward substitution). Triangular solves everywhere in the library are
 //   GEMMs against these block inverses — the standard GPU TRSM trade.
+#include <algorithm>
+
 #include "kernels.h"
+#include "potrf_plan.h"
 
 namespace {
 
@@ -45,218 +51,401 @@ __launch_bounds__(256) __global__ void trtri_block_lds_k(const S* L, S* T,
   }
 }
 
-// Fused factor + invert of one diagonal block, single workgroup.
+// ---- 64 x 64 factor + invert core -----------------------------------------
 //
-// Real BSZ=128: LDS = L[128][128] (131 KiB) + S scratch 64x64 (32 KiB) = the
-// full 160 KiB CU budget. The inverse T = L^-1 is computed blockwise with a
-// 64-split, recycling freed LDS regions of L:
-//   T11 = inv(L11) -> S -> (global, and copied over L11's region)
-//   W   = L21*T11  -> S   (L21 still live)
-//   T22 = inv(L22) -> L21's region -> global  (L21 dead after W)
-//   T21 = -T22*W   -> global
-// Complex BSZ=64: direct column-parallel inversion into S (both fit).
-// The dinv output block is always BSZ x BSZ, identity-extended when n < BSZ.
+// LDS images have a leading dimension of kImgLd = 65 elements, odd in units
+// of the element size: rows r and r+1 of one column sit one element apart in
+// the bank row, so a column-direction access by up to 32 (8-byte elements) or
+// 16 (16-byte elements) consecutive rows is conflict-free.
+constexpr int kB = dlaf::kPotrfBsz;  // 64
+constexpr int kImgLd = kB + 1;
+static_assert(kB == 64, "the core below is written for 64 x 64 blocks");
+
+template <typename S>
+using Img = S (*)[kImgLd];
+
+// value of lane `src` (the same for the whole wave, a constant once the
+// caller's loops are unrolled) as a wave-uniform value: no LDS round trip
+template <typename S>
+__device__ __forceinline__ S read_lane(S v, int src) {
+  constexpr int NW = sizeof(S) / 4;
+  int w[NW];
+  __builtin_memcpy(w, &v, sizeof(S));
+#pragma unroll
+  for (int q = 0; q < NW; ++q) w[q] = __builtin_amdgcn_readlane(w[q], src);
+  __builtin_memcpy(&v, w, sizeof(S));
+  return v;
+}
+
+// 1 / a on the critical path of the 16 x 16 factor: hardware estimate plus two
+// Newton steps (about 1 ulp) instead of the long IEEE division sequence.
+// a <= 0 or NaN gives a negative, infinite or NaN result, never a trap.
+__device__ __forceinline__ double pivot_rcp(double a) {
+  double x = __builtin_amdgcn_rcp(a);
+  double e = fma(-a, x, 1.0);
+  x = fma(x, e, x);
+  e = fma(-a, x, 1.0);
+  return fma(x, e, x);
+}
+__device__ __forceinline__ float pivot_rcp(float a) { return 1.0f / a; }
+
+// One wave, no barrier, no LDS traffic inside the loops: Cholesky of the
+// 16 x 16 diagonal block at (c0, c0) of L. Lane l holds ROW i = l & 15 of the
+// block in 16 registers (the four 16-lane groups hold copies), so U[i][p] is
+// the lane's own and U[j][p] is a readlane of the constant lane j.
 //
-// do_factor=0 skips the factorization phases (inverting an already-factored
-// received tile after a broadcast).
-template <typename S, int BSZ>
+// LDL^T-style elimination on unscaled columns
+//   U[i][j] -= (U[i][p] / U[p][p]) conj(U[j][p])   (p < j)
+// then L[:,j] = U[:,j] / sqrt(U[j][j]); rdiag[c0+j] = 1 / sqrt(U[j][j]) is
+// kept for the panel solve. A non-positive pivot only shows in that last
+// step, as a NaN column j: the columns before it stay exact. Entries above
+// the diagonal are carried along and never feed one on or below it.
+template <typename S>
+__device__ inline void factor16_wave(Img<S> L,
+                                     typename ScalarTraits<S>::real_t* rdiag,
+                                     int c0, int lane) {
+  using TR = ScalarTraits<S>;
+  using RT = typename TR::real_t;
+  const int i = lane & 15;
+  S u[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) u[j] = L[c0 + i][c0 + j];
+#pragma unroll
+  for (int p = 0; p < 15; ++p) {
+    const RT s = pivot_rcp(TR::real(read_lane(u[p], p)));
+    const S w = u[p] * s;
+#pragma unroll
+    for (int j = p + 1; j < 16; ++j)
+      u[j] -= w * TR::conj(read_lane(u[p], j));
+  }
+  RT dv = RT(0);
+#pragma unroll
+  for (int j = 0; j < 16; ++j)
+    if (i == j) dv = TR::real(u[j]);
+  const RT sc = RT(1) / sqrt(dv);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) u[j] = u[j] * read_lane(sc, j);
+  if (lane < 16) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (j <= i) L[c0 + i][c0 + j] = u[j];
+    rdiag[c0 + i] = sc;
+  }
+}
+
+// One wave: inverse of the lower-triangular 16 x 16 block at (c0, c0) of L
+// into the same place of T (strict upper part zero). Same lane layout;
+// row-oriented forward substitution, so the rows above a NaN row stay clean.
+template <typename S>
+__device__ inline void invert16_wave(Img<S> L, Img<S> T, int c0, int lane) {
+  using TR = ScalarTraits<S>;
+  const int i = lane & 15;
+  S l[16], t[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) l[j] = L[c0 + i][c0 + j];
+  S dv = TR::from_real(1);
+#pragma unroll
+  for (int j = 0; j < 16; ++j)
+    if (i == j) dv = l[j];
+  const S rd = TR::recip(dv);
+#pragma unroll
+  for (int c = 0; c < 16; ++c) t[c] = (c == i) ? rd : TR::zero();
+  // row p of T is final when step p starts: T[p][c] = rd_p (delta_pc - sum);
+  // rows i > p then take  t_i -= rd_i L[i][p] T[p][:]
+#pragma unroll
+  for (int p = 0; p < 15; ++p) {
+    const S f = rd * l[p];
+#pragma unroll
+    for (int c = 0; c <= p; ++c) {
+      const S tp = read_lane(t[c], p);
+      if (i > p) t[c] -= f * tp;
+    }
+  }
+  if (lane < 16) {
+#pragma unroll
+    for (int c = 0; c < 16; ++c)
+      T[c0 + i][c0 + c] = (c <= i) ? t[c] : TR::zero();
+  }
+}
+
+// Whole workgroup (256 threads). L holds the block: lower triangle live,
+// identity on and zero below the diagonal outside the live n x n part, strict
+// upper triangle never feeding a result. On return L holds the factor (if
+// do_factor) and T its full inverse (zero strict upper triangle, identity
+// outside the live part). Sc is a 32 x 33 scratch, rdiag holds 64 reals. T
+// needs no initialisation. The caller puts a barrier between its writes of L
+// and this call; the call ends on one.
+template <typename S>
+__device__ void factor_invert_core(Img<S> L, Img<S> T, S (*Sc)[33],
+                                   typename ScalarTraits<S>::real_t* rdiag,
+                                   int tid, int do_factor) {
+  using TR = ScalarTraits<S>;
+  for (int e = tid; e < kB * kImgLd; e += 256) (&T[0][0])[e] = TR::zero();
+  if (do_factor) {
+    for (int cb = 0; cb < 4; ++cb) {
+      const int c0 = cb * 16;
+      if (tid < 64) factor16_wave<S>(L, rdiag, c0, tid);
+      __syncthreads();
+      if (cb == 3) break;
+      // panel below the 16-block, X L_cc^H = A: one row per thread, in
+      // registers and in place (a thread reads and writes its own row only);
+      // right-looking, so the 15 - j updates of a step are independent
+      {
+        const int r = c0 + 16 + tid;
+        if (r < kB) {
+          S a[16];
+#pragma unroll
+          for (int p = 0; p < 16; ++p) a[p] = L[r][c0 + p];
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            a[j] = a[j] * rdiag[c0 + j];
+#pragma unroll
+            for (int q = j + 1; q < 16; ++q)
+              a[q] -= a[j] * TR::conj(L[c0 + q][c0 + j]);
+          }
+#pragma unroll
+          for (int p = 0; p < 16; ++p) L[r][c0 + p] = a[p];
+        }
+        __syncthreads();
+      }
+      // trailing update of the lower triangle, 16 x 16 sub-blocks, one
+      // element per thread per sub-block
+      {
+        const int t0 = c0 + 16, m = 3 - cb;
+        const int ti = tid >> 4, tj = tid & 15;
+        for (int bi = 0; bi < m; ++bi) {
+          S xi[16];
+#pragma unroll
+          for (int p = 0; p < 16; ++p) xi[p] = L[t0 + 16 * bi + ti][c0 + p];
+          for (int bj = 0; bj <= bi; ++bj) {
+            if (bj == bi && tj > ti) continue;
+            const int rj = t0 + 16 * bj + tj;
+            S acc = TR::zero();
+#pragma unroll
+            for (int p = 0; p < 16; ++p) acc += xi[p] * TR::conj(L[rj][c0 + p]);
+            L[t0 + 16 * bi + ti][rj] -= acc;
+          }
+        }
+        __syncthreads();
+      }
+    }
+  } else {
+    __syncthreads();  // T is zero before the diagonal blocks are written
+  }
+  // the four diagonal 16-blocks of the inverse are independent: one wave each
+  invert16_wave<S>(L, T, (tid >> 6) * 16, tid & 63);
+  __syncthreads();
+  // off-diagonal 16-blocks of the inverse by distance from the diagonal:
+  //   W = sum_P L_IP T_PJ (J <= P < I),  T_IJ = -T_II W
+  for (int dist = 1; dist < 4; ++dist) {
+    const int nblk = 4 - dist;
+    for (int e = tid; e < nblk * 256; e += 256) {
+      const int b = e >> 8, r = (e & 255) >> 4, c = e & 15;
+      const int I = (b + dist) * 16, J = b * 16;
+      S acc = TR::zero();
+      for (int p = J; p < I; ++p) acc += L[I + r][p] * T[p][J + c];
+      Sc[(b >> 1) * 16 + r][(b & 1) * 16 + c] = acc;
+    }
+    __syncthreads();
+    for (int e = tid; e < nblk * 256; e += 256) {
+      const int b = e >> 8, r = (e & 255) >> 4, c = e & 15;
+      const int I = (b + dist) * 16, J = b * 16;
+      S acc = TR::zero();
+      for (int p = 0; p <= r; ++p)
+        acc += T[I + r][I + p] * Sc[(b >> 1) * 16 + p][(b & 1) * 16 + c];
+      T[I + r][J + c] = -acc;
+    }
+    __syncthreads();
+  }
+}
+
+// store the live lower triangle of the factor and the whole inverse block
+template <typename S>
+__device__ inline void store_factor_and_inverse(Img<S> L, Img<S> T, S* A,
+                                                int n, int ld, S* Tout,
+                                                int tid, int store_factor) {
+  for (int e = tid; e < kB * kB; e += 256) {
+    const int i = e >> 6, j = e & 63;
+    if (store_factor && i < n && j <= i) A[(int64_t)i * ld + j] = L[i][j];
+    Tout[e] = T[i][j];
+  }
+}
+
+// Stand-alone entry: [factor +] invert the leading n x n (n <= 64) of A into
+// the 64 x 64 block Tout. Launch 0 of the tile factorization is this kernel.
+// do_factor=0 inverts an already-factored block (a tile received after a
+// broadcast); its strict upper triangle is not read.
+template <typename S>
 __launch_bounds__(256) __global__ void potrf_invert_block_k(S* A, int n,
                                                             int ld, S* Tout,
                                                             int do_factor) {
   using TR = ScalarTraits<S>;
-  using RT = typename TR::real_t;
-  constexpr int HB = BSZ / 2;
-  __shared__ S L[BSZ][BSZ];
-  __shared__ S Sc[HB][HB];  // no pad: L + Sc is exactly the 160 KiB CU budget
+  __shared__ S Li[kB][kImgLd];
+  __shared__ S Ti[kB][kImgLd];
+  __shared__ S Sc[32][33];
+  __shared__ typename TR::real_t Rd[kB];
   const int tid = threadIdx.x;
+  for (int e = tid; e < kB * kB; e += 256) {
+    const int i = e >> 6, j = e & 63;
+    Li[i][j] = (i < n && j <= i) ? A[(int64_t)i * ld + j]
+                                 : (i == j ? TR::from_real(1) : TR::zero());
+  }
+  __syncthreads();
+  factor_invert_core<S>(Li, Ti, Sc, Rd, tid, do_factor);
+  store_factor_and_inverse<S>(Li, Ti, A, n, ld, Tout, tid, do_factor);
+}
 
-  for (int e = tid; e < BSZ * BSZ; e += 256) {
-    const int i = e / BSZ, j = e % BSZ;
-    L[i][j] = (i < n && j < n) ? A[(int64_t)i * ld + j] : TR::zero();
+// Launch d >= 1 of the tile factorization: see potrf_plan.h for the
+// decomposition and for which workgroup owns which write.
+template <typename S>
+__launch_bounds__(256) __global__ void potrf_step_k(S* A, int n, int ld,
+                                                    S* dinv, S* side, int d,
+                                                    int nbk) {
+  using TR = ScalarTraits<S>;
+  namespace plan = dlaf::potrf_plan;
+  __shared__ S P0[kB][kImgLd];
+  __shared__ S P1[kB][kImgLd];
+  __shared__ S Sc[32][33];
+  __shared__ typename TR::real_t Rd[kB];
+  const int tid = threadIdx.x;
+  int I, J;
+  plan::block_of((int)blockIdx.x, nbk, d, &I, &J);
+  const int c = d - 1;
+  const int r0 = I * kB, s0 = J * kB, q0 = c * kB;  // tile rows / cols / panel col
+
+  // column d-2 of the tile <- side half (d-2)&1 (written by launch d-1)
+  for (int R = d - 1; R < nbk; ++R) {
+    if (!plan::copies_row(I, J, nbk, d, R)) continue;
+    const S* src = side + plan::side_offset((d - 2) & 1, R, nbk, kB);
+    for (int e = tid; e < kB * kB; e += 256) {
+      const int i = e >> 6, j = e & 63;
+      if (R * kB + i < n)
+        A[(int64_t)(R * kB + i) * ld + (q0 - kB) + j] = src[e];
+    }
+  }
+
+  // P0 <- A[I,c], P1 <- dinv[c]; block column c is full (c < nbk-1)
+  const S* Dc = dinv + (int64_t)c * kB * kB;
+  for (int e = tid; e < kB * kB; e += 256) {
+    const int i = e >> 6, j = e & 63;
+    P0[i][j] = (r0 + i < n) ? A[(int64_t)(r0 + i) * ld + q0 + j] : TR::zero();
+    P1[i][j] = Dc[e];
   }
   __syncthreads();
 
-  if (do_factor) {
-    const int ncb = (n + 15) / 16;
-    const int ti = tid / 16, tj = tid % 16;
-    for (int cb = 0; cb < ncb; ++cb) {
-      const int c0 = cb * 16;
-      const int bsz16 = min(16, n - c0);
-      // factor the 16x16 diagonal block with DEFERRED column scaling
-      // (LDL^T-style elimination on unscaled columns, one barrier per step:
-      //  U[i][j] -= U[i][p] conj(U[j][p]) / U[p][p], then L[:,j] = U[:,j] /
-      //  sqrt(U[j][j]) in one scale pass).
-      for (int p = 0; p < bsz16; ++p) {
-        const RT s = RT(1) / TR::real(L[c0 + p][c0 + p]);
-        if (ti < bsz16 && tj < bsz16 && tj > p && tj <= ti)
-          L[c0 + ti][c0 + tj] -= (L[c0 + ti][c0 + p] * TR::conj(L[c0 + tj][c0 + p])) * s;
-        __syncthreads();
-      }
-      // snapshot the column scale BEFORE any thread rewrites the diagonal
-      const bool act = (ti < bsz16 && tj < bsz16 && tj <= ti);
-      const RT sc = act ? RT(1) / sqrt(TR::real(L[c0 + tj][c0 + tj])) : RT(1);
-      __syncthreads();
-      if (act) L[c0 + ti][c0 + tj] = L[c0 + ti][c0 + tj] * sc;
-      __syncthreads();
-      // panel solve below the 16-block
-      {
-        const int r = c0 + 16 + tid;
-        if (r < n) {
-          for (int j = 0; j < bsz16; ++j) {
-            S x = L[r][c0 + j];
-            for (int p = 0; p < j; ++p) x -= L[r][c0 + p] * TR::conj(L[c0 + j][c0 + p]);
-            L[r][c0 + j] = x * (RT(1) / TR::real(L[c0 + j][c0 + j]));
-          }
+  // 4 x 4 outputs per thread: rows ty + 16a, columns tx + 16b
+  const int ty = tid >> 4, tx = tid & 15;
+  // X = P0 * dinv[c]^H; dinv[c] is lower triangular, so column block b of X
+  // needs p < 16 (b+1) only
+  auto panel_product = [&](S (&x)[4][4]) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) x[a][b] = TR::zero();
+#pragma unroll
+    for (int pb = 0; pb < 4; ++pb) {
+      for (int pp = 0; pp < 16; ++pp) {
+        const int p = pb * 16 + pp;
+        S av[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) av[a] = P0[ty + 16 * a][p];
+#pragma unroll
+        for (int b = pb; b < 4; ++b) {
+          const S dv = TR::conj(P1[tx + 16 * b][p]);
+#pragma unroll
+          for (int a = 0; a < 4; ++a) x[a][b] += av[a] * dv;
         }
-        __syncthreads();
-      }
-      // trailing update (lower)
-      {
-        const int t0 = c0 + 16;
-        const int nt = n - t0;
-        if (nt > 0) {
-          for (int e = tid; e < nt * nt; e += 256) {
-            const int i = e / nt, j = e % nt;
-            if (j <= i) {
-              S acc = L[t0 + i][c0] * TR::conj(L[t0 + j][c0]);
-              for (int p = 1; p < bsz16; ++p)
-                acc += L[t0 + i][c0 + p] * TR::conj(L[t0 + j][c0 + p]);
-              L[t0 + i][t0 + j] -= acc;
-            }
-          }
-        }
-        __syncthreads();
       }
     }
-    // store the factor (lower triangle)
-    for (int e = tid; e < BSZ * BSZ; e += 256) {
-      const int i = e / BSZ, j = e % BSZ;
-      if (i < n && j < n && j <= i) A[(int64_t)i * ld + j] = L[i][j];
-    }
-    // no barrier needed: inversion only reads LDS L, which is final
-  }
+  };
 
-  // ---- inversion ----
-  // initialize Tout = identity-extended zero (overwritten below where computed)
-  for (int e = tid; e < BSZ * BSZ; e += 256) {
-    const int i = e / BSZ, j = e % BSZ;
-    Tout[i * BSZ + j] = (i == j && i >= n) ? TR::from_real(1) : TR::zero();
-  }
-  __syncthreads();  // order init writes before the computed overwrites
-
-  if constexpr (BSZ == 64) {
-    // blocked-16 inversion: serial chains shrink from 64 to 16 steps (the
-    // direct column-parallel form was a ~2000-FMA dependent chain per thread
-    // and dominated the 108us kernel time); off-diagonal 16x16 blocks are
-    // thread-parallel products  T_IJ = -T_II * (sum_P L_IP T_PJ).
-    __shared__ S Tc[64][65];
-    for (int e = tid; e < 64 * 65; e += 256) Tc[e / 65][e % 65] = TR::zero();
-    __syncthreads();
-    // diagonal 16-blocks, one column per thread (64 threads, 16-step chains)
-    {
-      const int j = tid;
-      if (j < n) {
-        const int B0 = (j / 16) * 16;
-        const int bend = min(B0 + 16, n);
-        Tc[j][j] = TR::recip(L[j][j]);
-        for (int i = j + 1; i < bend; ++i) {
-          S acc = TR::zero();
-          for (int p = j; p < i; ++p) acc += L[i][p] * Tc[p][j];
-          Tc[i][j] = -(TR::recip(L[i][i]) * acc);
-        }
-      }
+  S xi[4][4], xj[4][4];
+  panel_product(xi);
+  __syncthreads();
+  if (I != J) {
+    for (int e = tid; e < kB * kB; e += 256) {
+      const int i = e >> 6, j = e & 63;
+      P0[i][j] = (s0 + i < n) ? A[(int64_t)(s0 + i) * ld + q0 + j] : TR::zero();
     }
     __syncthreads();
-    // off-diagonal blocks by distance d: W = sum_P L_IP T_PJ, T_IJ = -T_II W
-    for (int dist = 1; dist < 4; ++dist) {
-      const int nblk = 4 - dist;
-      // phase 1: W into Sc (block b at rows (b/2)*16, cols (b%2)*16)
-      for (int e = tid; e < nblk * 256; e += 256) {
-        const int b = e / 256, r = (e % 256) / 16, c = e % 16;
-        const int I = (b + dist) * 16, J = b * 16;
-        S acc = TR::zero();
-        for (int p = J; p < I; ++p) acc += L[I + r][p] * Tc[p][J + c];
-        Sc[(b / 2) * 16 + r][(b % 2) * 16 + c] = acc;
-      }
-      __syncthreads();
-      // phase 2: T_IJ = -T_II * W (T_II lower triangular)
-      for (int e = tid; e < nblk * 256; e += 256) {
-        const int b = e / 256, r = (e % 256) / 16, c = e % 16;
-        const int I = (b + dist) * 16, J = b * 16;
-        S acc = TR::zero();
-        for (int p = 0; p <= r; ++p)
-          acc += Tc[I + r][I + p] * Sc[(b / 2) * 16 + p][(b % 2) * 16 + c];
-        Tc[I + r][J + c] = -acc;
-      }
-      __syncthreads();
+    panel_product(xj);
+    __syncthreads();
+  }
+  // every read of A[I,c], A[J,c] and dinv[c] is done: P0 <- X_I, P1 <- X_J
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      P0[ty + 16 * a][tx + 16 * b] = xi[a][b];
+      P1[ty + 16 * a][tx + 16 * b] = (I != J) ? xj[a][b] : xi[a][b];
     }
-    for (int e = tid; e < BSZ * BSZ; e += 256) {
-      const int i = e / BSZ, j2 = e % BSZ;
-      if (i < n && j2 < n) Tout[i * BSZ + j2] = Tc[i][j2];
+  // X_I = L[I,c]: to the side half c&1, or in place in the last launch
+  if (plan::writes_side(I, J, nbk, d)) {
+    S* dst = side + plan::side_offset(c & 1, I, nbk, kB);
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        dst[(ty + 16 * a) * kB + tx + 16 * b] = xi[a][b];
+  } else if (plan::writes_panel_in_place(I, J, nbk, d)) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (r0 + ty + 16 * a < n)
+          A[(int64_t)(r0 + ty + 16 * a) * ld + q0 + tx + 16 * b] = xi[a][b];
+  }
+  __syncthreads();
+
+  // C = A[I,J] - X_I X_J^H
+  S cv[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int gr = r0 + ty + 16 * a, gc = s0 + tx + 16 * b;
+      const bool live = gr < n && gc < n && (I != J || gc <= gr);
+      cv[a][b] = live ? A[(int64_t)gr * ld + gc] : TR::zero();
     }
+  for (int q = 0; q < kB; ++q) {
+    S av[4], bv[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) av[a] = P0[ty + 16 * a][q];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) bv[b] = TR::conj(P1[tx + 16 * b][q]);
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) cv[a][b] -= av[a] * bv[b];
+  }
+
+  if (!plan::factors(I, J, d)) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int gr = r0 + ty + 16 * a, gc = s0 + tx + 16 * b;
+        if (gr < n && gc < n && (I != J || gc <= gr))
+          A[(int64_t)gr * ld + gc] = cv[a][b];
+      }
     return;
   }
 
-  // BSZ == 128: 64-split scheme
-  const int h = min(HB, n);
-  const int rest = n - h;
-  // T11 = inv(L11) -> Sc
-  {
-    const int j = tid;
-    if (j < h) {
-      for (int i = 0; i < j; ++i) Sc[i][j] = TR::zero();
-      Sc[j][j] = TR::recip(L[j][j]);
-      for (int i = j + 1; i < h; ++i) {
-        S acc = TR::zero();
-        for (int p = j; p < i; ++p) acc += L[i][p] * Sc[p][j];
-        Sc[i][j] = -(TR::recip(L[i][i]) * acc);
-      }
+  // workgroup (d,d): factor the updated block and write dinv[d]
+  __syncthreads();  // all reads of X from P0 / P1 are done
+  const int nl = min(kB, n - r0);
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int i = ty + 16 * a, j = tx + 16 * b;
+      P0[i][j] = (i < nl && j <= i) ? cv[a][b]
+                                    : (i == j ? TR::from_real(1) : TR::zero());
     }
-    __syncthreads();
-    for (int e = tid; e < h * h; e += 256) {
-      const int i = e / h, j2 = e % h;
-      Tout[i * BSZ + j2] = Sc[i][j2];
-    }
-  }
-  if (rest > 0) {
-    // W = L21 * T11 -> needs T11 (Sc) and L21 (L); write W over L11's region
-    // (L11 is dead). Then T22 = inv(L22) into Sc (Sc free after W copy? no —
-    // W lives in L11's region, Sc holds T11 still needed? T21 = -T22*W only
-    // needs W and T22. So: W -> L11 region, T22 -> Sc (overwrite T11).
-    __syncthreads();
-    for (int e = tid; e < rest * h; e += 256) {
-      const int i = e / h, j = e % h;
-      S acc = TR::zero();
-      for (int p = j; p < h; ++p) acc += L[h + i][p] * Sc[p][j];
-      L[i][j] = acc;  // W[i][j] stored in L11's region (row i < 64)
-    }
-    __syncthreads();
-    // T22 = inv(L22) -> Sc
-    {
-      const int j = tid;
-      if (j < rest) {
-        for (int i = 0; i < j; ++i) Sc[i][j] = TR::zero();
-        Sc[j][j] = TR::recip(L[h + j][h + j]);
-        for (int i = j + 1; i < rest; ++i) {
-          S acc = TR::zero();
-          for (int p = j; p < i; ++p) acc += L[h + i][h + p] * Sc[p][j];
-          Sc[i][j] = -(TR::recip(L[h + i][h + i]) * acc);
-        }
-      }
-      __syncthreads();
-      for (int e = tid; e < rest * rest; e += 256) {
-        const int i = e / rest, j2 = e % rest;
-        Tout[(h + i) * BSZ + (h + j2)] = Sc[i][j2];
-      }
-    }
-    // T21 = -T22 * W  (T22 in Sc, W in L11 region)
-    for (int e = tid; e < rest * h; e += 256) {
-      const int i = e / h, j = e % h;
-      S acc = TR::zero();
-      for (int p = 0; p <= i && p < rest; ++p) acc += Sc[i][p] * L[p][j];
-      Tout[(h + i) * BSZ + j] = -acc;
-    }
-  }
+  __syncthreads();
+  factor_invert_core<S>(P0, P1, Sc, Rd, tid, 1);
+  store_factor_and_inverse<S>(P0, P1, A + (int64_t)r0 * ld + r0, nl, ld,
+                              dinv + (int64_t)d * kB * kB, tid, 1);
 }
 
 template <typename S>
@@ -284,8 +473,22 @@ __global__ void trtri_lower_k(const S* L, S* T, int n, int ldl, int ldt,
 template <typename S>
 void dlaf::potrf_invert_block(S* A, int n, int ld, S* Tout, int do_factor,
                               hipStream_t stream) {
-  potrf_invert_block_k<S, kPotrfBsz>
-      <<<1, 256, 0, stream>>>(A, n, ld, Tout, do_factor);
+  potrf_invert_block_k<S><<<1, 256, 0, stream>>>(A, n, ld, Tout, do_factor);
+}
+
+// One launch per block column (potrf_plan.h); nothing but the stream orders
+// them, and nothing is allocated or copied from the host.
+template <typename S>
+void dlaf::potrf_tile_fused(S* A, int n, int ld, S* dinv, S* side,
+                            hipStream_t stream) {
+  namespace plan = dlaf::potrf_plan;
+  if (n <= 0) return;
+  const int nbk = plan::nblocks(n, kPotrfBsz);
+  potrf_invert_block_k<S>
+      <<<1, 256, 0, stream>>>(A, std::min(n, kPotrfBsz), ld, dinv, 1);
+  for (int d = 1; d < nbk; ++d)
+    potrf_step_k<S>
+        <<<plan::grid(nbk, d), 256, 0, stream>>>(A, n, ld, dinv, side, d, nbk);
 }
 
 template <typename S>
@@ -303,6 +506,7 @@ void dlaf::trtri_lower(const S* L, S* T, int n, int ldl, int ldt,
 
 #define INSTANTIATE(S)                                                       \
   template void dlaf::potrf_invert_block(S*, int, int, S*, int, hipStream_t); \
+  template void dlaf::potrf_tile_fused(S*, int, int, S*, S*, hipStream_t);    \
   template void dlaf::trtri_lower(const S*, S*, int, int, int, int, hipStream_t);
 INSTANTIATE(double)
 INSTANTIATE(float)

@@ -37,10 +37,10 @@ struct GemmDesc {
 namespace dlaf {
 
 // Diagonal-block size of the tile Cholesky (dinv blocks are kPotrfBsz^2).
-// 64 for every dtype: the fused factor+invert kernel then needs ~73 KiB LDS
-// and can co-reside with trailing-update GEMM blocks on a CU — a 128-block
-// (160 KiB) kernel can never be scheduled next to them and serializes the
-// lookahead.
+// 64 for every dtype: the factor+invert kernels then need ~73 KiB LDS in
+// double (~147 KiB in cplx<double>) and can co-reside with trailing-update
+// GEMM blocks on a CU — a 128-block (160 KiB) kernel can never be scheduled
+// next to them and serializes the lookahead.
 constexpr int kPotrfBsz = 64;
 
 // ---- fused batched GEMM (MFMA f64 / f32), csrc/gemm_tiles.hip ----
@@ -90,6 +90,17 @@ bool bt_apply_group(S* E, int64_t nE, int64_t npad, const S* V, const S* VTt,
 template <typename S>
 void potrf_invert_block(S* A, int n, int ld, S* Tout, int do_factor,
                         hipStream_t stream);
+
+// In-place lower Cholesky of the leading n x n of a tile (row stride ld) in
+// ceil(n / kPotrfBsz) stream-ordered launches (decomposition: potrf_plan.h).
+// dinv[d] (kPotrfBsz^2 elements each) receives the identity-extended inverse
+// of diagonal block d; `side` is a workspace of potrf_plan::side_elems()
+// elements that needs no clearing and carries nothing between calls. The
+// strict upper triangle of the tile is neither read nor written. The first
+// failed pivot leaves a NaN on its diagonal; columns before it are exact.
+template <typename S>
+void potrf_tile_fused(S* A, int n, int ld, S* dinv, S* side,
+                      hipStream_t stream);
 
 // Column-parallel inverse of a lower-triangular n x n block (arbitrary n;
 // single LDS-resident workgroup when it fits): T = L^-1, T may not alias L.

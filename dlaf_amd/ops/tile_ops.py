@@ -165,29 +165,22 @@ def dinv_workspace(nb: int, dtype: torch.dtype, device) -> torch.Tensor:
     return torch.empty((nblocks, bsz, bsz), dtype=dtype, device=device)
 
 
-_POTRF_DESC_CACHE = {}
+_POTRF_SIDE_CACHE = {}
 
 
-def _potrf_descs(n: int, ld: int, dtype: torch.dtype, device) -> torch.Tensor:
-    """Device descriptor table for potrf_tile's internal panel/trailing GEMMs.
-
-    Rows 2d (panel X = A21*dinv^H) and 2d+1 (trailing A22 -= X X^H) per
-    diagonal block d; offsets relative to the tile base pointer, so one table
-    serves every tile of the same (n, ld, dtype)."""
-    key = (n, ld, dtype, str(device))
-    t = _POTRF_DESC_CACHE.get(key)
+def potrf_side_workspace(nb: int, dtype: torch.dtype, device) -> torch.Tensor:
+    """Side workspace of the fused tile Cholesky (two halves of nb x bsz, see
+    csrc/potrf_plan.h), cached per (nb, dtype, device) and per stream: it
+    carries nothing between calls, but two calls running at once must not
+    share one."""
+    device = torch.device(device)
+    key = (nb, dtype, str(device), torch.cuda.current_stream(device).cuda_stream)
+    t = _POTRF_SIDE_CACHE.get(key)
     if t is None:
         bsz = potrf_bsz(dtype)
-        nblocks = (n + bsz - 1) // bsz
-        rows = []
-        for d in range(nblocks):
-            c0 = d * bsz
-            panel_off = (c0 + bsz) * ld + c0
-            trail_off = (c0 + bsz) * ld + (c0 + bsz)
-            rows.append([panel_off, panel_off, 0, 1, 0, 0])
-            rows.append([trail_off, panel_off, panel_off, 1, 0, 0])
-        t = torch.tensor(rows, dtype=torch.int64).reshape(-1).to(device)
-        _POTRF_DESC_CACHE[key] = t
+        nblocks = (nb + bsz - 1) // bsz
+        t = torch.empty((2, nblocks * bsz, bsz), dtype=dtype, device=device)
+        _POTRF_SIDE_CACHE[key] = t
     return t
 
 
@@ -202,8 +195,8 @@ def potrf_tile(tile: torch.Tensor, dinv: Optional[torch.Tensor] = None) -> Optio
     if tile.is_cuda:
         if dinv is None:
             dinv = dinv_workspace(n, tile.dtype, tile.device)
-        ddesc = _potrf_descs(n, tile.stride(0), tile.dtype, tile.device)
-        get_ext().potrf_tile(tile, n, tile.stride(0), dinv, ddesc)
+        side = potrf_side_workspace(n, tile.dtype, tile.device)
+        get_ext().potrf_tile(tile, n, tile.stride(0), dinv, side)
         return dinv
     L, inf = torch.linalg.cholesky_ex(tile)
     tile.copy_(L)
