@@ -84,7 +84,6 @@ def _secular_roots(d: torch.Tensor, z: torch.Tensor, rho: float,
     jj = idx                                          # left pole index = j
     j2 = (idx + 1).clamp(max=k - 1)                   # right pole (last: unused)
     last = idx == k - 1
-    dscale = float(d.abs().max()) + rho
     for it in range(iters):
         diff = delta0 - mu.unsqueeze(0)              # d_i - lam_j
         t = z2.unsqueeze(1) / diff
@@ -92,8 +91,13 @@ def _secular_roots(d: torch.Tensor, z: torch.Tensor, rho: float,
         f = 1.0 + rho * t.sum(0)
         if it >= 12 and it % 6 == 0:
             # vectorized convergence check (one sync every 6 iterations)
+            # the Newton step |f / f'| is judged against the root's own
+            # offset from its pole, not against max|d| + rho: an absolute
+            # test passed roots in 1e-12-wide pole clusters at 1e-3 of
+            # their gap, and z-hat with them at 1e-9
             fp_est = rho * t2.sum(0)
-            if float((f.abs() / fp_est.clamp_min(1e-300)).max()) < 1e-15 * dscale:
+            step = f.abs() / fp_est.clamp_min(1e-300)
+            if float((step / mu.abs().clamp_min(1e-300)).max()) < 1e-15:
                 break
         psi_p = torch.where(below, t2, torch.zeros_like(t2)).sum(0)
         phi_p = torch.where(below, torch.zeros_like(t2), t2).sum(0)
@@ -160,6 +164,32 @@ def _secular_roots(d: torch.Tensor, z: torch.Tensor, rho: float,
     # final: return the bracket point with smaller |f|
     mu = torch.where(flo.abs() < fhi.abs(), lo, hi)
     return sidx, mu
+
+
+def _secular_eigvecs(dk: torch.Tensor, zk: torch.Tensor, rho: float,
+                     sidx: torch.Tensor, mu: torch.Tensor
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lam [k], U [k, k]): eigenpairs of diag(dk) + rho zk zk^T from the
+    secular roots lam_j = dk[sidx_j] + mu_j, columns of U normalized."""
+    lam = dk[sidx] + mu
+    # delta[i, j] = d_i - lam_j, via exact pole differences
+    delta = (dk.unsqueeze(1) - dk[sidx].unsqueeze(0)) - mu.unsqueeze(0)
+    # Gu/Eisenstat z-hat:
+    #   zh_i^2 = prod_j (lam_j - d_i) / (rho * prod_{j!=i} (d_j - d_i))
+    dd = dk.unsqueeze(1) - dk.unsqueeze(0)       # d_j - d_i at [i, j]
+    num = (-delta).abs().clamp_min(1e-300).log().sum(1)
+    # the diagonal j == i is excluded BEFORE the sum: summing its
+    # log(1e-300) = -690.8 and subtracting it afterwards cancelled with an
+    # absolute error of 690 eps, i.e. ~150 eps relative in zh
+    den_m = dd.abs().clamp_min(1e-300).log()
+    den_m.diagonal().zero_()
+    den = den_m.sum(1)
+    zh = torch.exp(0.5 * (num - den - math.log(rho)))
+    zh = torch.where(zk < 0, -zh, zh)
+    # eigenvectors of the rank-1 system
+    U = zh.unsqueeze(1) / delta                  # [k, k]
+    U = U / torch.linalg.vector_norm(U, dim=0, keepdim=True)
+    return lam, U
 
 
 def _merge(w1, Q1, w2, Q2, rho, device):
@@ -296,20 +326,7 @@ def _merge(w1, Q1, w2, Q2, rho, device):
         dk = torch.from_numpy(dn[nd_idx]).to(sec_dev)
         zk = torch.from_numpy(zn[nd_idx]).to(sec_dev)
         sidx, mu = _secular_roots(dk, zk, rho_eff)
-        lam = dk[sidx] + mu
-        # delta[i, j] = d_i - lam_j, via exact pole differences
-        delta = (dk.unsqueeze(1) - dk[sidx].unsqueeze(0)) - mu.unsqueeze(0)
-        # Gu/Eisenstat z-hat:
-        #   zh_i^2 = prod_j (lam_j - d_i) / (rho * prod_{j!=i} (d_j - d_i))
-        dd = dk.unsqueeze(1) - dk.unsqueeze(0)       # d_j - d_i at [i, j]
-        num = (-delta).abs().clamp_min(1e-300).log().sum(1)
-        den_m = dd.abs().clamp_min(1e-300).log()
-        den = den_m.sum(1) - torch.diagonal(den_m)
-        zh = torch.exp(0.5 * (num - den - math.log(rho_eff)))
-        zh = torch.where(zk < 0, -zh, zh)
-        # eigenvectors of the rank-1 system
-        U = zh.unsqueeze(1) / delta                  # [k1, k1]
-        U = U / torch.linalg.vector_norm(U, dim=0, keepdim=True)
+        lam, U = _secular_eigvecs(dk, zk, rho_eff, sidx, mu)
         lam_out = lam.to(device)
         V_nd = Qnd @ U.to(Qnd.dtype).to(device)
     else:
