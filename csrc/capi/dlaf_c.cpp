@@ -280,6 +280,56 @@ int run_sposv(int ctx, char uplo, int n, int nrhs, const void* a,
   }
 }
 
+// LU of the leading n x n part in place; ipiv[n] gets 1-based global rows
+int run_getrf(int ctx, int n, void* a, const struct DLAF_descriptor& da,
+              int* ipiv, const char* dtype) {
+  Gil g;
+  try {
+    auto av = np_view(ctx, a, da, dtype);
+    return capi_->attr("dlaf_lu_factorization")(
+        ctx, av, desc_obj(leading(da, n, n)), np_vec(ipiv, n, "int32"))
+        .cast<int>();
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: lu factorization failed: %s\n", e.what());
+    return -1;
+  }
+}
+
+int run_getrs(int ctx, char trans, int n, int nrhs, const void* a,
+              const struct DLAF_descriptor& da, const int* ipiv, void* b,
+              const struct DLAF_descriptor& db, const char* dtype) {
+  Gil g;
+  try {
+    auto av = np_view(ctx, const_cast<void*>(a), da, dtype);
+    auto bv = np_view(ctx, b, db, dtype);
+    return capi_->attr("dlaf_lu_solve")(
+        ctx, std::string(1, trans), av, desc_obj(leading(da, n, n)),
+        np_vec(const_cast<int*>(ipiv), n, "int32"), bv,
+        desc_obj(leading(db, n, nrhs))).cast<int>();
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: lu solve failed: %s\n", e.what());
+    return -1;
+  }
+}
+
+int run_gecon(int ctx, char norm, int n, const void* a,
+              const struct DLAF_descriptor& da, double anorm, double* rcond,
+              const char* dtype) {
+  Gil g;
+  try {
+    auto av = np_view(ctx, const_cast<void*>(a), da, dtype);
+    *rcond = capi_->attr("dlaf_lu_rcond")(
+        ctx, std::string(1, norm), av, desc_obj(leading(da, n, n)), anorm)
+        .cast<double>();
+    return 0;
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "dlaf_c: lu condition estimate failed: %s\n",
+                 e.what());
+    *rcond = std::nan("");
+    return -1;
+  }
+}
+
 struct DLAF_descriptor from_sl(int n, const int d[9], int m = -1) {
   struct DLAF_descriptor out;
   out.m = m >= 0 ? m : d[2];
@@ -596,5 +646,46 @@ DLAF_PORFS(dlaf_pzporfs, dlaf_complex_z, "complex128")
 DLAF_SPOSV(dlaf_pdsposv, double, "float64")
 DLAF_SPOSV(dlaf_pzcposv, dlaf_complex_z, "complex128")
 #undef DLAF_SPOSV
+
+#define DLAF_GETRF(name, T, dtype)                                            \
+  void name(int m, int n, T* a, int ia, int ja, const int desca[9],           \
+            int* ipiv, int* info) {                                           \
+    (void)ia; (void)ja;                                                       \
+    *info = m == n ? run_getrf(sl_grid(), n, a, from_sl(n, desca), ipiv,      \
+                               dtype)                                         \
+                   : -1;                                                      \
+  }
+DLAF_GETRF(dlaf_pdgetrf, double, "float64")
+DLAF_GETRF(dlaf_pzgetrf, dlaf_complex_z, "complex128")
+#undef DLAF_GETRF
+
+#define DLAF_GETRS(name, T, dtype)                                            \
+  void name(char trans, int n, int nrhs, const T* a, int ia, int ja,          \
+            const int desca[9], const int* ipiv, T* b, int ib, int jb,        \
+            const int descb[9], int* info) {                                  \
+    (void)ia; (void)ja; (void)ib; (void)jb;                                   \
+    *info = run_getrs(sl_grid(), trans, n, nrhs, a, from_sl(n, desca), ipiv,  \
+                      b, from_sl(nrhs, descb), dtype);                        \
+  }
+DLAF_GETRS(dlaf_pdgetrs, double, "float64")
+DLAF_GETRS(dlaf_pzgetrs, dlaf_complex_z, "complex128")
+#undef DLAF_GETRS
+
+void dlaf_pdgecon(char norm, int n, const double* a, int ia, int ja,
+                  const int desca[9], double anorm, double* rcond, int* info) {
+  (void)ia; (void)ja;
+  *info = run_gecon(sl_grid(), norm, n, a, from_sl(n, desca), anorm, rcond,
+                    "float64");
+}
+
+void dlaf_pdgesv(int n, int nrhs, double* a, int ia, int ja,
+                 const int desca[9], int* ipiv, double* b, int ib, int jb,
+                 const int descb[9], int* info) {
+  (void)ia; (void)ja; (void)ib; (void)jb;
+  *info = run_getrf(sl_grid(), n, a, from_sl(n, desca), ipiv, "float64");
+  if (*info == 0)
+    *info = run_getrs(sl_grid(), 'N', n, nrhs, a, from_sl(n, desca), ipiv, b,
+                      from_sl(nrhs, descb), "float64");
+}
 
 }  // extern "C"

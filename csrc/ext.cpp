@@ -577,6 +577,71 @@ void hemv_tiles(torch::Tensor storage, torch::Tensor x, torch::Tensor y,
   HIP_CHECK(hipGetLastError());
 }
 
+// ---- LU panel and row interchanges over the tile storage (lu_panel.hip) ----
+
+// Factors tile column k of the square storage [nt, nt, nb, nb] in place with
+// partial pivoting; ipiv [>= n] int32 (0-based) and info [1] int32 stay on
+// the device.
+void lu_panel(torch::Tensor storage, int64_t n, int64_t k, torch::Tensor ipiv,
+              torch::Tensor info) {
+  TORCH_CHECK(storage.is_cuda() && storage.dim() == 4 &&
+              storage.is_contiguous() && storage.size(0) == storage.size(1) &&
+              storage.size(2) == storage.size(3),
+              "storage must be a contiguous [nt, nt, nb, nb] device tensor");
+  const int64_t nt = storage.size(0), nb = storage.size(2);
+  TORCH_CHECK(nb > 0 && nt * nb < (1LL << 21),
+              "matrix too large for the LU panel kernel");
+  TORCH_CHECK(n >= 0 && n <= nt * nb && n > (nt - 1) * nb,
+              "n does not match the storage");
+  TORCH_CHECK(k >= 0 && k < std::max<int64_t>(nt, 1), "bad tile column");
+  TORCH_CHECK(ipiv.scalar_type() == at::kInt && ipiv.is_contiguous() &&
+              ipiv.dim() == 1 && ipiv.size(0) >= n &&
+              ipiv.device() == storage.device(),
+              "ipiv must be a contiguous int32 vector of length n on the "
+              "storage's device");
+  TORCH_CHECK(info.scalar_type() == at::kInt && info.numel() == 1 &&
+              info.device() == storage.device(),
+              "info must be one int32 on the storage's device");
+  if (nt == 0 || k * nb >= n) return;
+  auto ws = torch::empty({dlaf::lu_panel_work_elems(n)}, storage.options());
+  auto wsrow = torch::empty({dlaf::lu_panel_work_rows(n)},
+                            storage.options().dtype(torch::kInt32));
+  dispatch_dtype(storage.scalar_type(), [&](auto tag) {
+    using S = typename decltype(tag)::type;
+    dlaf::lu_panel(ptr<S>(storage), (int)nt, (int)nb, n, (int)k,
+                   ipiv.data_ptr<int32_t>(), info.data_ptr<int32_t>(),
+                   ptr<S>(ws), wsrow.data_ptr<int32_t>(), cur_stream());
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
+// Swaps rows s and ipiv[s] for s in [s0, s1) (backwards when reverse) in the
+// element columns [c0, c1) of a contiguous [lr, lc, mb, nb] storage.
+void laswp_tiles(torch::Tensor storage, torch::Tensor ipiv, int64_t s0,
+                 int64_t s1, int64_t c0, int64_t c1, bool reverse) {
+  TORCH_CHECK(storage.is_cuda() && storage.dim() == 4 &&
+              storage.is_contiguous(),
+              "storage must be a contiguous [lr, lc, mb, nb] device tensor");
+  const int64_t lr = storage.size(0), lc = storage.size(1),
+                mb = storage.size(2), nb = storage.size(3);
+  TORCH_CHECK(lr * mb < (1LL << 31) && lc * nb < (1LL << 31),
+              "matrix too large for the interchange kernel");
+  TORCH_CHECK(ipiv.scalar_type() == at::kInt && ipiv.is_contiguous() &&
+              ipiv.dim() == 1 && ipiv.device() == storage.device(),
+              "ipiv must be a contiguous int32 vector on the storage's device");
+  TORCH_CHECK(0 <= s0 && s0 <= s1 && s1 <= ipiv.size(0) && s1 <= lr * mb,
+              "bad pivot range");
+  TORCH_CHECK(0 <= c0 && c0 <= c1 && c1 <= lc * nb, "bad column range");
+  if (s1 == s0 || c1 == c0) return;
+  dispatch_dtype(storage.scalar_type(), [&](auto tag) {
+    using S = typename decltype(tag)::type;
+    dlaf::laswp_tiles(ptr<S>(storage), (int)lr, (int)lc, (int)mb, (int)nb,
+                      ipiv.data_ptr<int32_t>(), s0, s1, c0, c1,
+                      reverse ? 1 : 0, cur_stream());
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
 
 // csrc/band_chase.cpp
@@ -615,6 +680,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Hermitian in the uplo triangle of a local tile storage, read once",
         py::arg("storage"), py::arg("x"), py::arg("y"), py::arg("yabs"),
         py::arg("n"), py::arg("uplo"));
+  m.def("lu_panel", &lu_panel,
+        "in-place LU with partial pivoting of tile column k of a square "
+        "local tile storage; one launch per column, pivots and the "
+        "zero-pivot record stay on the device",
+        py::arg("storage"), py::arg("n"), py::arg("k"), py::arg("ipiv"),
+        py::arg("info"));
+  m.def("laswp_tiles", &laswp_tiles,
+        "row interchanges ipiv[s0:s1] on element columns [c0, c1) of a local "
+        "tile storage, one thread per column",
+        py::arg("storage"), py::arg("ipiv"), py::arg("s0"), py::arg("s1"),
+        py::arg("c0"), py::arg("c1"), py::arg("reverse"));
+  m.attr("LU_W") = dlaf::kLuW;
   m.def("hemv_work_size", &dlaf::hemv_work_size,
         "doubles of workspace hemv_tiles uses", py::arg("nt"), py::arg("nb"));
   m.def("sturm_interval", &sturm_interval,

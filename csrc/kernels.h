@@ -196,4 +196,33 @@ void hemv_tiles(const S* a, const S* x, S* y,
                 typename ScalarTraits<S>::real_t* yabs, int nt, int nb,
                 int64_t n, int uplo, double* work, hipStream_t stream);
 
+// ---- LU with partial pivoting over the tile storage, csrc/lu_panel.hip ----
+// lu_panel factors tile column k of the square [nt, nt, nb, nb] storage a in
+// place: rows k*nb .. n-1, columns k*nb .. min((k+1)*nb, n)-1, pivot = the
+// first row of the largest CABS1 value (LAPACK's i?amax). ipiv[g] (0-based
+// row, >= g) is written for the panel's columns g; *info receives g + 1 of the
+// first exactly-zero pivot while it is still 0 (the column is left unscaled
+// and the factorization goes on). The interchanges are applied to the
+// panel's own columns only. ws / wsrow hold lu_panel_work_elems(n) elements /
+// lu_panel_work_rows(n) int32 and need no clearing. One launch per column
+// plus four per inner block of kLuW columns, all on the stream; nothing is
+// read back. Rows and columns at or beyond n are neither read into a result
+// nor written. k*nb >= n launches nothing.
+constexpr int kLuW = 32;
+constexpr int kLuRows = 256;
+int64_t lu_panel_work_elems(int64_t n);
+int64_t lu_panel_work_rows(int64_t n);
+template <typename S>
+void lu_panel(S* a, int nt, int nb, int64_t n, int k, int32_t* ipiv,
+              int32_t* info, S* ws, int32_t* wsrow, hipStream_t stream);
+
+// Row interchanges on a [lr, lc, mb, nbc] storage: for s in [s0, s1) (from
+// s1-1 down when reverse), rows s and ipiv[s] (0-based) swap in the element
+// columns [c0, c1). One thread per column; a pivot outside the storage's
+// rows is skipped. An empty range launches nothing.
+template <typename S>
+void laswp_tiles(S* a, int lr, int lc, int mb, int nbc, const int32_t* ipiv,
+                 int64_t s0, int64_t s1, int64_t c0, int64_t c1, int reverse,
+                 hipStream_t stream);
+
 }  // namespace dlaf

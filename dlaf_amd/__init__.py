@@ -25,7 +25,8 @@ Public API (mirrors the reference's free-function API):
     condition estimates triangular_rcond, cholesky_rcond (with
     TriangularVectorSolver, inverse_norm_estimate) and cholesky_solve, and the
     refinement layer cholesky_refine, cholesky_solve_expert,
-    cholesky_solve_mixed (with HermitianVectorProduct, cholesky_info)
+    cholesky_solve_mixed (with HermitianVectorProduct, cholesky_info), and the
+    general-matrix layer lu_factorization, lu_solve, general_solve, lu_rcond
 """
 
 from .types import Side, UpLo, Op, Diag  # noqa: F401
@@ -56,6 +57,12 @@ from .algs.refine import (  # noqa: F401
     cholesky_refine,
     cholesky_solve_expert,
     cholesky_solve_mixed,
+)
+from .algs.lu import (  # noqa: F401
+    lu_factorization,
+    lu_solve,
+    general_solve,
+    lu_rcond,
 )
 from .algs.eigensolver import (  # noqa: F401
     hermitian_eigensolver,

@@ -5,8 +5,9 @@ grid management by integer context, ScaLAPACK-style descriptors, and
 ``p?potrf / p?potri / p?trtri / p?syevd / p?heevd / p?sygvd / p?hegvd``
 entry points, the norms ``p?lange / p?lansy / p?lanhe / p?lantr``, the
 condition estimates ``p?pocon / p?trcon``, the solve ``p?potrs``, its
-refinement ``p?porfs`` and the mixed-precision solves ``pdsposv / pzcposv``, all
-operating on the caller's LOCAL block-cyclic column-major buffer (numpy or
+refinement ``p?porfs`` and the mixed-precision solves ``pdsposv / pzcposv``, and
+the general-matrix ``p?getrf / p?getrs / p?gesv / p?gecon`` (single-rank
+contexts), all operating on the caller's LOCAL block-cyclic column-major buffer (numpy or
 torch). Each call wraps the buffer into a tiled ``Matrix``
 (mirrored to the GPU when available), runs the native algorithm, and copies
 the result back — the flow of the reference's ``src/c_api/eigensolver/
@@ -25,7 +26,8 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from .types import UpLo, Diag
+from .types import UpLo, Diag, Op
+from .core.asserts import dlaf_assert
 from .core.distribution import Distribution
 from .comm.grid import CommGrid
 from .matrix.matrix import Matrix
@@ -37,6 +39,7 @@ from .algs.tridiag_bisect import (hermitian_eigenvalues,
 from .algs.norm import matrix_norm
 from .algs.condition import cholesky_rcond, triangular_rcond, cholesky_solve
 from .algs.refine import cholesky_info, cholesky_refine, cholesky_solve_mixed
+from .algs.lu import lu_factorization, lu_solve, lu_rcond
 
 
 @dataclass
@@ -408,6 +411,69 @@ def dlaf_cholesky_solve_mixed(ctx: int, uplo: str, a_local,
     return iters, info
 
 
+# ---- LU with partial pivoting (single-rank contexts) ----
+
+_TRANS_CHAR = {"N": Op.NoTrans, "T": Op.Trans, "C": Op.ConjTrans}
+
+
+def _single_rank(grid: CommGrid, what: str) -> None:
+    dlaf_assert(not grid.distributed,
+                f"{what}: LU is not implemented on a multi-rank "
+                "(distributed) grid; use a 1 x 1 context",
+                (grid.grid_rows, grid.grid_cols))
+
+
+def _ipiv_in(ipiv, n: int, device) -> torch.Tensor:
+    """The caller's 1-based pivots as the library's 0-based int32 vector."""
+    t = torch.as_tensor(ipiv).reshape(-1)[:n]
+    return (t.to(torch.int64) - 1).to(device=device, dtype=torch.int32)
+
+
+def dlaf_lu_factorization(ctx: int, a_local, desc: DLAF_descriptor,
+                          ipiv_out) -> int:
+    """``P A = L U`` in place on ``a_local`` (``lu_factorization``).
+    ``ipiv_out`` ([n] int32 buffer) receives the 1-based global row indices
+    of LAPACK / ScaLAPACK: row j was interchanged with row ``ipiv[j - 1]``.
+    Returns info: 0, or the 1-based index of the first zero pivot."""
+    grid = _grid(ctx)
+    _single_rank(grid, "dlaf_lu_factorization")
+    mat = _wrap_local(a_local, desc, grid, _device_for(grid))
+    ipiv, info = lu_factorization(mat)
+    out = torch.as_tensor(ipiv_out)
+    out.reshape(-1)[: desc.n] = (ipiv + 1).to(device=out.device,
+                                               dtype=out.dtype)
+    _unwrap_local(mat, a_local)
+    return info
+
+
+def dlaf_lu_solve(ctx: int, trans: str, a_local, desca: DLAF_descriptor,
+                  ipiv, b_local, descb: DLAF_descriptor) -> int:
+    """Solve op(A) X = B with the factors and 1-based pivots of
+    ``dlaf_lu_factorization`` (both only read); trans 'N' / 'T' / 'C';
+    ``b_local`` is overwritten with X."""
+    grid = _grid(ctx)
+    _single_rank(grid, "dlaf_lu_solve")
+    dev = _device_for(grid)
+    fac = _wrap_local(a_local, desca, grid, dev)
+    rhs = _wrap_local(b_local, descb, grid, dev)
+    lu_solve(_TRANS_CHAR[str(trans).upper()], fac,
+             _ipiv_in(ipiv, desca.n, dev), rhs)
+    _unwrap_local(rhs, b_local)
+    return 0
+
+
+def dlaf_lu_rcond(ctx: int, norm: str, a_local, desc: DLAF_descriptor,
+                  anorm: float) -> float:
+    """Estimated reciprocal condition number ('1' / 'O' or 'I') of the matrix
+    whose LU factors are in ``a_local`` (only read); ``anorm`` is that norm
+    of the matrix before it was factored."""
+    grid = _grid(ctx)
+    _single_rank(grid, "dlaf_lu_rcond")
+    mat = _wrap_local(a_local, desc, grid, _device_for(grid))
+    return lu_rcond(_NORM_CHAR.get(str(norm).upper(), norm), mat,
+                    float(anorm))
+
+
 # ---- ScaLAPACK-style shims (reference dlaf_c/...: dlaf_p{s,d,c,z}potrf etc.) ----
 
 def _sl_desc(n, mb, nb, uplo_n=None, m=None) -> DLAF_descriptor:
@@ -525,6 +591,42 @@ def pXsposv(ctx: int, uplo: str, n: int, nrhs: int, a_local, ia: int, ja: int,
                                      _norm_desc(descx, n, nrhs))
 
 
+def pXgetrf(ctx: int, m: int, n: int, a_local, ia: int, ja: int,
+            desca: DLAF_descriptor, ipiv_out) -> int:
+    """p?getrf for square matrices; ipiv 1-based global row indices."""
+    assert (ia, ja) == (1, 1) and m == n, "square matrices at (1, 1) only"
+    return dlaf_lu_factorization(ctx, a_local, _norm_desc(desca, n, n),
+                                 ipiv_out)
+
+
+def pXgetrs(ctx: int, trans: str, n: int, nrhs: int, a_local, ia: int,
+            ja: int, desca: DLAF_descriptor, ipiv, b_local, ib: int, jb: int,
+            descb: DLAF_descriptor) -> int:
+    assert (ia, ja) == (1, 1) and (ib, jb) == (1, 1)
+    return dlaf_lu_solve(ctx, trans, a_local, _norm_desc(desca, n, n), ipiv,
+                         b_local, _norm_desc(descb, n, nrhs))
+
+
+def pXgecon(ctx: int, norm: str, n: int, a_local, ia: int, ja: int,
+            desca: DLAF_descriptor, anorm: float) -> float:
+    """rcond of p?gecon (its workspace arguments have no counterpart)."""
+    assert (ia, ja) == (1, 1)
+    return dlaf_lu_rcond(ctx, norm, a_local, _norm_desc(desca, n, n), anorm)
+
+
+def pXgesv(ctx: int, n: int, nrhs: int, a_local, ia: int, ja: int,
+           desca: DLAF_descriptor, ipiv_out, b_local, ib: int, jb: int,
+           descb: DLAF_descriptor) -> int:
+    """p?gesv: factor, then solve unless info > 0 (B is then untouched)."""
+    assert (ia, ja) == (1, 1) and (ib, jb) == (1, 1)
+    da = _norm_desc(desca, n, n)
+    info = dlaf_lu_factorization(ctx, a_local, da, ipiv_out)
+    if info == 0:
+        dlaf_lu_solve(ctx, "N", a_local, da, ipiv_out, b_local,
+                      _norm_desc(descb, n, nrhs))
+    return info
+
+
 # dtype-suffixed aliases matching the reference's C symbol names
 dlaf_pdpotrf = dlaf_pspotrf = dlaf_pcpotrf = dlaf_pzpotrf = pXpotrf
 dlaf_pdpotri = dlaf_pspotri = dlaf_pcpotri = dlaf_pzpotri = pXpotri
@@ -542,3 +644,7 @@ dlaf_pdtrcon = dlaf_pstrcon = dlaf_pctrcon = dlaf_pztrcon = pXtrcon
 dlaf_pdpotrs = dlaf_pspotrs = dlaf_pcpotrs = dlaf_pzpotrs = pXpotrs
 dlaf_pdporfs = dlaf_psporfs = dlaf_pcporfs = dlaf_pzporfs = pXporfs
 dlaf_pdsposv = dlaf_pzcposv = pXsposv
+dlaf_pdgetrf = dlaf_psgetrf = dlaf_pcgetrf = dlaf_pzgetrf = pXgetrf
+dlaf_pdgetrs = dlaf_psgetrs = dlaf_pcgetrs = dlaf_pzgetrs = pXgetrs
+dlaf_pdgecon = dlaf_psgecon = dlaf_pcgecon = dlaf_pzgecon = pXgecon
+dlaf_pdgesv = dlaf_psgesv = dlaf_pcgesv = dlaf_pzgesv = pXgesv

@@ -379,3 +379,93 @@ def trsm_panel_right_lowerH(
             mb, bs, bs, ld, bsz, ld,
             Op.NoTrans, opc, 1.0, 0.0, inplace=True,
         )
+
+
+# ---------------- LU with partial pivoting ----------------
+
+def _cabs1(x: torch.Tensor) -> torch.Tensor:
+    """|re| + |im|: the magnitude LAPACK's i?amax compares."""
+    return x.real.abs() + x.imag.abs() if x.is_complex() else x.abs()
+
+
+def lu_panel(storage: torch.Tensor, n: int, k: int, ipiv: torch.Tensor,
+             info: torch.Tensor) -> None:
+    """In-place LU with partial pivoting of tile column ``k`` of the square
+    storage ``[nt, nt, nb, nb]``: rows ``k*nb .. n-1``, columns ``k*nb ..
+    min((k+1)*nb, n)-1``. The pivot of a column is the FIRST row of the
+    largest CABS1 value; a zero pivot leaves its column unscaled and puts its
+    1-based index into ``info`` (one int32) unless one is there already.
+    ``ipiv[g]`` (int32, 0-based) is set for the panel's columns; the
+    interchanges are applied to the panel's own columns only.
+
+    GPU: csrc/lu_panel.hip (a missing extension raises). CPU: the same rule
+    in plain torch, column by column."""
+    if storage.is_cuda:
+        get_ext().lu_panel(storage, n, k, ipiv, info)
+        return
+    nt, nb = storage.shape[0], storage.shape[2]
+    g0 = k * nb
+    m = n - g0
+    if m <= 0:
+        return
+    nc = min(nb, m)
+    P = storage[k:, k].reshape(-1, nb)[:m, :nc].clone()
+    for j in range(nc):
+        p = j + int(torch.argmax(_cabs1(P[j:, j])))  # first maximum
+        ipiv[g0 + j] = g0 + p
+        if p != j:
+            P[[j, p]] = P[[p, j]]
+        piv = P[j, j]
+        if piv == 0:
+            if int(info[0]) == 0:
+                info[0] = g0 + j + 1
+            continue
+        P[j + 1:, j] = P[j + 1:, j] / piv
+        if j + 1 < nc:
+            P[j + 1:, j + 1:] -= torch.outer(P[j + 1:, j], P[j, j + 1:])
+    for i in range(k, nt):
+        r0 = (i - k) * nb
+        rows = min(nb, m - r0)
+        storage[i, k, :rows, :nc] = P[r0:r0 + rows]
+
+
+def laswp(storage: torch.Tensor, ipiv: torch.Tensor, s0: int, s1: int,
+          c0: int, c1: int, reverse: bool = False) -> None:
+    """Row interchanges on a ``[lr, lc, mb, nb]`` tile storage: for s in
+    ``[s0, s1)`` (from ``s1 - 1`` down when ``reverse``) rows s and
+    ``ipiv[s]`` (0-based) swap in the element columns ``[c0, c1)``."""
+    if s1 <= s0 or c1 <= c0:
+        return
+    if storage.is_cuda:
+        get_ext().laswp_tiles(storage, ipiv, s0, s1, c0, c1, reverse)
+        return
+    mb, nb = storage.shape[2], storage.shape[3]
+    piv = ipiv[s0:s1].tolist()
+    order = range(s1 - 1, s0 - 1, -1) if reverse else range(s0, s1)
+    for s in order:
+        p = piv[s - s0]
+        if p == s:
+            continue
+        x = storage[s // mb, :, s % mb, :]
+        y = storage[p // mb, :, p % mb, :]
+        for j in range(c0 // nb, (c1 - 1) // nb + 1):
+            lo, hi = max(c0 - j * nb, 0), min(c1 - j * nb, nb)
+            tmp = x[j, lo:hi].clone()
+            x[j, lo:hi] = y[j, lo:hi]
+            y[j, lo:hi] = tmp
+
+
+def pivots_to_permutation(ipiv: torch.Tensor) -> torch.Tensor:
+    """int64 ``perm`` with ``(P B)[i] = B[perm[i]]`` for the interchanges
+    ``ipiv`` applied in order: the interchanges run once on the index vector
+    (on the device through ``laswp``'s kernel, nothing read back)."""
+    n = ipiv.shape[0]
+    if ipiv.is_cuda:
+        v = torch.arange(n, dtype=torch.float64, device=ipiv.device)
+        if n:
+            laswp(v.view(1, 1, n, 1), ipiv, 0, n, 0, 1)
+        return v.to(torch.int64)
+    perm = list(range(n))
+    for j, p in enumerate(ipiv.tolist()):
+        perm[j], perm[p] = perm[p], perm[j]
+    return torch.tensor(perm, dtype=torch.int64)

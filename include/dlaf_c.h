@@ -196,6 +196,35 @@ void dlaf_pzcposv(char uplo, int n, int nrhs, const dlaf_complex_z* a, int ia,
                   int jb, const int descb[9], dlaf_complex_z* x, int ix,
                   int jx, const int descx[9], int* iter, int* info);
 
+/* LU with partial pivoting (ScaLAPACK p?getrf / p?getrs / p?gecon / p?gesv
+ * without the workspace arguments) on a 1 x 1 grid; every i / j = 1, m = n.
+ * getrf overwrites a with its factors (unit-lower L below the diagonal, U on
+ * and above it); ipiv[n] receives 1-based global row indices: row j was
+ * interchanged with row ipiv[j - 1]. *info = 0, or the index of the first
+ * exactly-zero pivot (the factorization is completed regardless), or -1 on a
+ * bad argument. getrs overwrites b (n x nrhs) with the solution of
+ * op(A) X = B, trans 'N' / 'T' / 'C'; a and ipiv as getrf left them, only
+ * read. gecon: norm '1' / 'O' or 'I', anorm that norm of the matrix before
+ * it was factored (p?lange); *rcond is the estimated reciprocal condition
+ * number (0 for a singular U, 1 for n = 0). gesv = getrf, then getrs unless
+ * *info > 0 (b is then left untouched). */
+void dlaf_pdgetrf(int m, int n, double* a, int ia, int ja, const int desca[9],
+                  int* ipiv, int* info);
+void dlaf_pzgetrf(int m, int n, dlaf_complex_z* a, int ia, int ja,
+                  const int desca[9], int* ipiv, int* info);
+void dlaf_pdgetrs(char trans, int n, int nrhs, const double* a, int ia, int ja,
+                  const int desca[9], const int* ipiv, double* b, int ib,
+                  int jb, const int descb[9], int* info);
+void dlaf_pzgetrs(char trans, int n, int nrhs, const dlaf_complex_z* a, int ia,
+                  int ja, const int desca[9], const int* ipiv,
+                  dlaf_complex_z* b, int ib, int jb, const int descb[9],
+                  int* info);
+void dlaf_pdgecon(char norm, int n, const double* a, int ia, int ja,
+                  const int desca[9], double anorm, double* rcond, int* info);
+void dlaf_pdgesv(int n, int nrhs, double* a, int ia, int ja,
+                 const int desca[9], int* ipiv, double* b, int ib, int jb,
+                 const int descb[9], int* info);
+
 #ifdef __cplusplus
 }
 #endif

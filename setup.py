@@ -30,6 +30,7 @@ setup(
                 "csrc/norms.hip",
                 "csrc/trsv.hip",
                 "csrc/hemv.hip",
+                "csrc/lu_panel.hip",
                 "csrc/rocblas_batch.cpp",
                 "csrc/chase_gpu.hip",
             ],
