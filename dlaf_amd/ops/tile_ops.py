@@ -265,8 +265,10 @@ def tri_inverse_full(A: torch.Tensor, lower: bool, unit: bool = False) -> torch.
     if A.is_cuda:
         if lower:
             return _tri_inv_lower_gpu(A, unit)
-        tmp = A.mH.contiguous()
-        return _tri_inv_lower_gpu(tmp, unit).mH.contiguous()
+        # resolve_conj: for n == 1 the adjoint view is already contiguous, so
+        # contiguous() alone leaves a lazy conjugate bit the kernel never sees
+        tmp = A.mH.contiguous().resolve_conj()
+        return _tri_inv_lower_gpu(tmp, unit).mH.contiguous().resolve_conj()
     eye = torch.eye(n, dtype=A.dtype, device=A.device)
     if unit:
         tri = torch.tril(A, -1) + eye if lower else torch.triu(A, 1) + eye
