@@ -165,6 +165,53 @@ void potrf_tile(torch::Tensor A, int64_t n, int64_t ld, torch::Tensor dinv,
   HIP_CHECK(hipGetLastError());
 }
 
+// Dtypes with the single-launch panel TRSM (csrc/trsm_panel.hip); the others
+// solve their panels through batch_gemm.
+bool trsm_panel_supported(torch::Tensor t) {
+  return t.scalar_type() == at::kDouble || t.scalar_type() == at::kFloat;
+}
+
+// X <- X * tril(L)^-T for the ntiles = tile_offs.numel() tiles (mb x nb, row
+// stride ld) at element offsets tile_offs (device int64) into base; dinv as
+// potrf_tile fills it. strip: 0 = the kernel's own choice, else 16 or 32.
+void trsm_panel(torch::Tensor base, torch::Tensor tile_offs, torch::Tensor L,
+                int64_t ldl, torch::Tensor dinv, int64_t mb, int64_t nb,
+                int64_t ld, int64_t strip) {
+  TORCH_CHECK(base.is_cuda() && L.is_cuda() && dinv.is_cuda() &&
+              dinv.is_contiguous(), "tensors must be on GPU");
+  TORCH_CHECK(tile_offs.is_cuda() && tile_offs.scalar_type() == at::kLong &&
+              tile_offs.is_contiguous() && tile_offs.dim() == 1,
+              "tile_offs must be contiguous 1-d int64 on GPU");
+  TORCH_CHECK(trsm_panel_supported(base), "trsm_panel: dtype has no kernel");
+  TORCH_CHECK(L.scalar_type() == base.scalar_type() &&
+              dinv.scalar_type() == base.scalar_type(), "dtype mismatch");
+  TORCH_CHECK(mb >= 1 && nb >= 1 && mb < (int64_t(1) << 30) &&
+              nb < (int64_t(1) << 30) && ld >= nb && ldl >= nb, "bad shape");
+  TORCH_CHECK(strip == 0 || strip == 16 || strip == 32,
+              "strip must be 0, 16 or 32");
+  constexpr int bsz = kPotrfBsz;
+  const int64_t nblocks = (nb + bsz - 1) / bsz;
+  TORCH_CHECK(dinv.numel() >= nblocks * bsz * bsz, "dinv too small");
+  TORCH_CHECK(L.storage_offset() + (nb - 1) * ldl + nb <=
+              (int64_t)(L.storage().nbytes() / L.element_size()),
+              "L view exceeds its storage");
+  TORCH_CHECK((mb - 1) * ld + nb <= base.numel(), "tile exceeds base");
+  const int nt = (int)tile_offs.numel();
+  if (nt == 0) return;
+  auto s = cur_stream();
+  dispatch_dtype(base.scalar_type(), [&](auto tag) {
+    using S = typename decltype(tag)::type;
+    if constexpr (std::is_same_v<S, double> || std::is_same_v<S, float>) {
+      const int st = strip ? (int)strip : dlaf::trsm_panel_strip(nt, (int)mb);
+      dlaf::trsm_panel_fused_strip(ptr<S>(base), tile_offs.data_ptr<int64_t>(),
+                                   nt, ptr<const S>(L), (int)ldl,
+                                   ptr<const S>(dinv), (int)mb, (int)nb,
+                                   (int)ld, st, s);
+    }
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 // Factor (optional) + invert ONE bsz-block of a tile view; Tout = dinv[d].
 void factor_invert_block(torch::Tensor A, int64_t n, int64_t ld,
                          torch::Tensor Tout, bool do_factor) {
@@ -714,5 +761,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "rocBLAS pointer-array batched GEMM (uniform tile shape)");
   m.def("potrf_tile", &potrf_tile,
         "in-place tile Cholesky + diagonal-block inverses");
+  m.def("trsm_panel", &trsm_panel,
+        "single-launch panel TRSM X <- X * tril(L)^-T over a tile list",
+        py::arg("base"), py::arg("tile_offs"), py::arg("L"), py::arg("ldl"),
+        py::arg("dinv"), py::arg("mb"), py::arg("nb"), py::arg("ld"),
+        py::arg("strip") = 0);
+  m.def("trsm_panel_supported", &trsm_panel_supported,
+        "whether the tensor's dtype has the single-launch panel TRSM");
   m.attr("POTRF_BSZ") = kPotrfBsz;
 }

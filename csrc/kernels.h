@@ -108,6 +108,32 @@ template <typename S>
 void trtri_lower(const S* L, S* T, int n, int ldl, int ldt, int unit_diag,
                  hipStream_t stream);
 
+// ---- single-launch panel TRSM, csrc/trsm_panel.hip ----
+// S = double or float. Every tile t at base + tile_offs[t] (mb x nb, row
+// stride ld; tile_offs device-resident, in elements) is overwritten with
+// X * tril(L)^-T by the blocked recurrence over kPotrfBsz-wide column blocks
+//   X[:, d] = (X[:, d] - X[:, :d] * L[d, :d]^T) * dinv[d]^T,
+// dinv[d] the identity-extended inverse of diagonal block d as potrf_tile_fused
+// writes it. L is read strictly below its block diagonal only: its diagonal
+// blocks and strict upper triangle never reach the result. One plain launch
+// of ntiles * ceil(mb / strip) workgroups, each owning its rows for the whole
+// solve (no workgroup reads what another writes); nothing is read back and
+// ntiles <= 0 launches nothing. Any mb, nb >= 1; rows and columns outside
+// mb x nb are neither read into a result nor written. Tiles may not overlap
+// each other, L or dinv. The strip height (16 or 32 rows) comes from
+// trsm_panel_strip, a function of (ntiles, mb) alone, so a given call shape
+// always takes the same summation order; trsm_panel_fused_strip takes it
+// explicitly (tools/microbench.py).
+int trsm_panel_strip(int ntiles, int mb);
+template <typename S>
+void trsm_panel_fused(S* base, const int64_t* tile_offs, int ntiles,
+                      const S* L, int ldl, const S* dinv, int mb, int nb,
+                      int ld, hipStream_t stream);
+template <typename S>
+void trsm_panel_fused_strip(S* base, const int64_t* tile_offs, int ntiles,
+                            const S* L, int ldl, const S* dinv, int mb, int nb,
+                            int ld, int strip, hipStream_t stream);
+
 // ---- GPU bulge chase band -> tridiagonal, csrc/chase_gpu.hip ----
 template <typename S>
 void chase_gpu(S* a, int64_t ld, int64_t size, int64_t b, S* vstore,

@@ -8,9 +8,10 @@ Counterpart of the reference's ``factorization/cholesky/impl.h`` (local
             A_ij -= L_ik * L_jk^H              (trailing HERK/GEMM, i >= j > k)
 
 MI355X-native differences from the reference:
-* per-tile task flood -> FUSED kernels: the whole panel solve is a handful of
-  launches and the whole trailing update is ONE launch per k (descriptor list
-  over the rank's local tiles);
+* per-tile task flood -> FUSED kernels: the whole panel solve is ONE launch
+  per k in the real dtypes (csrc/trsm_panel.hip; a handful of launches in the
+  complex ones) and the whole trailing update is ONE launch per k (descriptor
+  list over the rank's local tiles);
 * panel TRSM runs against diagonal-block inverses computed during potrf_tile
   (TRSM-as-GEMM, csrc/factor.hip);
 * every GemmDesc for the whole factorization is precomputed and uploaded to
@@ -64,13 +65,19 @@ def _compute_dinv(diag: torch.Tensor, dinv: torch.Tensor) -> torch.Tensor:
 
 
 class _DescTable:
-    """All GemmDescs of a factorization, device-resident, sliced per step."""
+    """All GemmDescs of a factorization, device-resident, sliced per step,
+    and next to them the per-step tile-offset lists of the single-launch
+    panel TRSM (one flat int64 array)."""
 
     def __init__(self):
         self._rows: List[np.ndarray] = []
         self._index: Dict = {}
         self._dev: Optional[torch.Tensor] = None
         self._n = 0
+        self._offs: List[np.ndarray] = []
+        self._offs_index: Dict = {}
+        self._offs_dev: Optional[torch.Tensor] = None
+        self._noffs = 0
 
     def add(self, key, rows: np.ndarray):
         if len(rows) == 0:
@@ -79,11 +86,28 @@ class _DescTable:
         self._rows.append(rows)
         self._n += len(rows)
 
+    def add_offs(self, key, offs: np.ndarray):
+        if len(offs) == 0:
+            return
+        self._offs_index[key] = (self._noffs, len(offs))
+        self._offs.append(np.asarray(offs, dtype=np.int64))
+        self._noffs += len(offs)
+
     def upload(self, device):
         if self._n:
             cat = np.concatenate(self._rows, axis=0)
             self._dev = torch.from_numpy(cat).to(device)
+        if self._noffs:
+            self._offs_dev = torch.from_numpy(np.concatenate(self._offs)).to(device)
         self._rows = None
+        self._offs = None
+
+    def get_offs(self, key) -> Optional[torch.Tensor]:
+        loc = self._offs_index.get(key)
+        if loc is None:
+            return None
+        s, n = loc
+        return self._offs_dev[s : s + n]
 
     def get(self, key) -> Optional[torch.Tensor]:
         loc = self._index.get(key)
@@ -108,8 +132,13 @@ _PLAN_CACHE: Dict = _BoundedCache()
 
 
 def _trsm_plan_rows(table: _DescTable, key_prefix, offs: np.ndarray, nb: int,
-                    ld_l: int, bsz: int) -> None:
-    """Descs for the blocked panel TRSM-as-GEMM (per inner block d)."""
+                    ld_l: int, bsz: int, dtype) -> None:
+    """The panel solve's device-resident plan: the tile-offset list for the
+    single-launch kernel where ``dtype`` has it, else the descs of the blocked
+    TRSM-as-GEMM (per inner block d)."""
+    if ops.has_trsm_panel_fused(dtype):
+        table.add_offs((key_prefix, "trsm"), offs)
+        return
     nblocks = (nb + bsz - 1) // bsz
     for d in range(nblocks):
         c0 = d * bsz
@@ -121,6 +150,10 @@ def _trsm_plan_rows(table: _DescTable, key_prefix, offs: np.ndarray, nb: int,
 def _run_trsm_panel(table: _DescTable, key_prefix, base: torch.Tensor,
                     L_diag: torch.Tensor, dinv: torch.Tensor, nb: int,
                     opc: Op) -> None:
+    offs = table.get_offs((key_prefix, "trsm"))
+    if offs is not None:
+        ops.trsm_panel_fused(base, offs, L_diag, dinv, nb, nb, nb)
+        return
     bsz = dinv.shape[-1]
     nblocks = (nb + bsz - 1) // bsz
     ld_l = L_diag.stride(0)
@@ -154,7 +187,7 @@ def _local_plan(mat: Matrix) -> _DescTable:
         rows = np.arange(k + 1, nt)
         offs = np.array([mat.tile_offset((int(i), k)) for i in rows], dtype=np.int64)
         if len(offs):
-            _trsm_plan_rows(table, ("k", k), offs, nb, nb, bsz)
+            _trsm_plan_rows(table, ("k", k), offs, nb, nb, bsz, mat.dtype)
             # trailing split for lookahead:
             #   head = next panel column (j == k+1), factored eagerly on the
             #          high-priority stream so potrf(k+1) is not blocked;
@@ -400,7 +433,7 @@ def _dist_plan(mat: Matrix) -> _DescTable:
         if d.rank_col == kc and lr - li0 > 0:
             rows_g = [d.global_tile_of_local((li, 0))[0] for li in range(li0, lr)]
             offs = np.array([mat.tile_offset((i, k)) for i in rows_g], dtype=np.int64)
-            _trsm_plan_rows(table, ("k", k), offs, nb, nb, bsz)
+            _trsm_plan_rows(table, ("k", k), offs, nb, nb, bsz, mat.dtype)
         # trailing on local tiles, split for lookahead: head = global col k+1
         # (unblocks step k+1's panel), tail = the bulk
         lj0 = d.next_local_tile_col(k + 1)

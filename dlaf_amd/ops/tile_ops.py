@@ -340,6 +340,25 @@ def tri_mask(A: torch.Tensor, lower: bool, unit: bool = False) -> torch.Tensor:
     return torch.tril(A) if lower else torch.triu(A)
 
 
+def has_trsm_panel_fused(dtype: torch.dtype) -> bool:
+    """Whether ``dtype`` has the single-launch panel TRSM kernel
+    (csrc/trsm_panel.hip): the real types. The others run the blocked solve
+    as ``gemm_fused`` launches."""
+    return dtype in (torch.float64, torch.float32)
+
+
+def trsm_panel_fused(panel_base: torch.Tensor, tile_offs: torch.Tensor,
+                     L_diag: torch.Tensor, dinv: torch.Tensor, mb: int,
+                     nb: int, ld: int, strip: int = 0) -> None:
+    """X <- X * tril(L)^-H in ONE launch for the tiles (mb x nb, row stride
+    ``ld``) at the element offsets ``tile_offs`` (device int64, each tile
+    inside ``panel_base``: the kernel cannot check them). ``strip`` = 0 leaves
+    the strip height to the kernel."""
+    assert L_diag.stride(1) == 1
+    get_ext().trsm_panel(panel_base.reshape(-1), tile_offs, L_diag,
+                         L_diag.stride(0), dinv, mb, nb, ld, strip)
+
+
 def trsm_panel_right_lowerH(
     panel_base: torch.Tensor,
     tile_offs: Sequence[int],
@@ -348,16 +367,33 @@ def trsm_panel_right_lowerH(
     mb: int,
     nb: int,
     ld: int,
+    fused: Optional[bool] = None,
 ) -> None:
     """Solve X * op(L)^H = X for every panel tile in place (L lower-triangular).
 
     GPU blocked algorithm per inner block d (bsz = dinv block size):
-        X[:, d] -= X[:, :d] @ L[d, :d]^H        (fused over all panel tiles)
-        X[:, d]  = X[:, d] @ dinv[d]^H          (fused, in place)
-    This is the panel step of right-looking Cholesky (reference
-    ``factorization/cholesky/impl.h:151-189`` trsmPanelTile).
+        X[:, d] -= X[:, :d] @ L[d, :d]^H
+        X[:, d]  = X[:, d] @ dinv[d]^H
+    Real dtypes run all of it in one launch (``trsm_panel_fused``); complex
+    dtypes, and ``fused=False``, run two ``gemm_fused`` launches per block,
+    each fused over all panel tiles. This is the panel step of right-looking
+    Cholesky (reference ``factorization/cholesky/impl.h:151-189``
+    trsmPanelTile).
     """
     assert panel_base.is_cuda
+    if fused is None:
+        fused = has_trsm_panel_fused(panel_base.dtype)
+    if fused:
+        offs = np.asarray(tile_offs, dtype=np.int64)
+        if len(offs) == 0:
+            return
+        assert offs.min() >= 0 and \
+            int(offs.max()) + (mb - 1) * ld + nb <= panel_base.numel(), \
+            "tile outside the panel base"
+        trsm_panel_fused(panel_base,
+                         torch.from_numpy(offs).to(panel_base.device),
+                         L_diag, dinv, mb, nb, ld)
+        return
     opc = Op.ConjTrans if is_complex(panel_base.dtype) else Op.Trans
     bsz = dinv.shape[-1]
     nblocks = (nb + bsz - 1) // bsz

@@ -23,6 +23,7 @@ setup(
                 "csrc/gemm_tiles_v2.hip",
                 "csrc/bt_apply.hip",
                 "csrc/factor.hip",
+                "csrc/trsm_panel.hip",
                 "csrc/panel_qr.hip",
                 "csrc/secular.hip",
                 "csrc/bisect.hip",

@@ -5,7 +5,9 @@
 reading the stored triangle once at 6.3 TB/s and against
 ``hermitian_multiplication`` on n x nrhs (the per-column crossover).
 ``--mixed [n nb]``: ``cholesky_solve_mixed`` against the float64
-factorization and solve. Either runs alone, without the default list."""
+factorization and solve. ``--trsm``: the Cholesky panel solve, gemm_fused
+launches against the single-launch kernel. Each runs alone, without the
+default list."""
 
 import os
 import sys
@@ -248,6 +250,52 @@ def bench_mixed_solve(dtype=torch.float64, n=16384, nb=512, nrhs=4):
           f"iters={out['r'][1]} info={out['r'][2]}", flush=True)
 
 
+def bench_trsm_panel(dtype=torch.float64, nb=512, tiles=(1, 8, 31, 63)):
+    """Solo time of the Cholesky panel solve X <- X L^-T at nb: the
+    gemm_fused path (two launches per 64-column block) against the
+    single-launch kernel at each strip height (0 = the kernel's own choice).
+    Timed with events over ``inner`` back-to-back solves in place; L is scaled
+    to singular values around 1 so that X stays in range."""
+    a = torch.randn(nb, nb, dtype=dtype, device="cuda")
+    L = a @ a.mH + nb * torch.eye(nb, dtype=dtype, device="cuda")
+    dinv = ops.potrf_tile(L)
+    L = torch.tril(L) / (2 * nb) ** 0.5   # singular values around 1
+    dinv = dinv * 0
+    bsz = dinv.shape[-1]
+    for d in range((nb + bsz - 1) // bsz):
+        c0 = d * bsz
+        ops.get_ext().trtri_lower(L[c0:, c0:], dinv[d], min(bsz, nb - c0),
+                                  L.stride(0), bsz, False)
+    inner = 10
+    for nt in tiles:
+        x = torch.randn(nt, nb, nb, dtype=dtype, device="cuda")
+        offs = [i * nb * nb for i in range(nt)]
+        doffs = torch.tensor(offs, device="cuda")
+        fl = nt * nb ** 3 * (2 if dtype.is_complex else 1) * inner
+
+        def timed(fn):
+            for _ in range(2):
+                fn()
+            ts = []
+            for _ in range(5):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(inner):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ts.append(e0.elapsed_time(e1))
+            return sorted(ts)[len(ts) // 2]
+
+        ms = timed(lambda: ops.trsm_panel_right_lowerH(x, offs, L, dinv, nb, nb, nb, fused=False))
+        line = f"trsm_panel {dtype} nb={nb} tiles={nt}: gemm_fused {ms / inner * 1e3:.0f} us"
+        if ops.has_trsm_panel_fused(dtype):
+            for strip in (0, 16, 32):
+                ms = timed(lambda: ops.trsm_panel_fused(x, doffs, L, dinv, nb, nb, nb, strip=strip))
+                line += f" | strip {strip}: {ms / inner * 1e3:.0f} us ({fl / ms / 1e9:.1f} TF/s)"
+        print(line, flush=True)
+
+
 def _shape_args(flag, n, nb):
     rest = sys.argv[sys.argv.index(flag) + 1:]
     nums = []
@@ -260,6 +308,10 @@ def _shape_args(flag, n, nb):
 
 if __name__ == "__main__":
     print(torch.cuda.get_device_name(0))
+    if "--trsm" in sys.argv:
+        bench_trsm_panel(torch.float64)
+        bench_trsm_panel(torch.float32)
+        sys.exit(0)
     if "--hemv" in sys.argv or "--mixed" in sys.argv:
         if "--hemv" in sys.argv:
             n, nb = _shape_args("--hemv", 32768, 512)

@@ -32,6 +32,9 @@ def main():
     is_block = lambda n: "potrf_invert_block_k" in n
     is_step = lambda n: "potrf_step_k" in n
     is_gemm = lambda n: "gemm_v2_k" in n or "gemm_tiles_k" in n
+    # the single-launch panel solve (csrc/trsm_panel.hip); builds without it
+    # solve the panel with gemm_tiles_k launches
+    is_trsm = lambda n: "trsm_panel_k" in n
     fused = any(is_step(r[2]) for r in rows)
     # index of the kernel that opens each potrf_tile
     opens = []
@@ -48,7 +51,8 @@ def main():
         i1 = opens[k + 1] if k + 1 < nt else len(rows)
         seg = rows[i0:i1]
         q = seg[0][4]
-        chain = [r for r in seg if r[4] == q and (is_block(r[2]) or is_step(r[2]) or is_gemm(r[2]))]
+        chain = [r for r in seg if r[4] == q and (is_block(r[2]) or is_step(r[2])
+                                                  or is_gemm(r[2]) or is_trsm(r[2]))]
         # potrf_tile = up to the last diagonal-block / step kernel (parent build:
         # plus the small GEMMs between them)
         last_diag = max(j for j, r in enumerate(chain) if is_block(r[2]) or is_step(r[2]))
