@@ -52,12 +52,16 @@ def _hegst_diag_tile(a: torch.Tensor, l: torch.Tensor) -> None:
         ops.gemm_items(a, tmp, linv, [(0, 0, 0)], nb, Op.NoTrans, opc, 1.0, 0.0)
     else:
         a.copy_(linv @ ah @ linv.mH)
+    if a.is_complex():
+        a.diagonal().imag.zero_()   # Hermitian result: real diagonal (?hegs2)
 
 
 def generalized_to_standard(uplo: UpLo, mat_a: Matrix, mat_l: Matrix,
                             grid: Optional[CommGrid] = None) -> None:
     """In-place HEGST (itype=1): A <- inv(L) A inv(L)^H (Lower) or
-    A <- inv(U)^H A inv(U) (Upper storage, native on the local path)."""
+    A <- inv(U)^H A inv(U) (Upper storage, native on the local path).
+    Of A only the ``uplo`` triangle is read, and of its diagonal only the
+    real part (as LAPACK ``?hegst``); the diagonal comes back real."""
     if uplo == UpLo.Upper:
         g = grid if grid is not None else mat_a.grid
         if g is None or not g.distributed:
@@ -188,8 +192,9 @@ def generalized_to_standard(uplo: UpLo, mat_a: Matrix, mat_l: Matrix,
 
 
 def _herm_full_u(t: torch.Tensor) -> torch.Tensor:
-    """Full Hermitian tile from UPPER storage."""
-    return torch.triu(t) + torch.triu(t, 1).mH
+    """Full Hermitian tile from UPPER storage. As in ``_herm_full``, the
+    imaginary part of the stored diagonal is never read: it is dropped."""
+    return _herm_full(t, lower=False)
 
 
 def _hegst_local_upper(mat_a: Matrix, mat_u: Matrix) -> None:
@@ -220,6 +225,8 @@ def _hegst_local_upper(mat_a: Matrix, mat_u: Matrix) -> None:
         T1 = torch.linalg.solve_triangular(Ukk.mH, Ah, upper=False)
         sta[k, k] = torch.linalg.solve_triangular(
             Ukk.mH, T1.mH, upper=False).mH
+        if sta.is_complex():
+            sta[k, k].diagonal().imag.zero_()
         if k + 1 >= nt:
             break
         Akk_h = _herm_full_u(sta[k, k])

@@ -32,12 +32,19 @@ from .triangular import (
 
 
 def _herm_full(tile: torch.Tensor, lower: bool) -> torch.Tensor:
-    """Hermitian completion of a diagonal tile stored in one triangle."""
+    """Hermitian completion of a diagonal tile stored in one triangle.
+
+    Contract (BLAS ``?hemm``, LAPACK ``?hegst``, ``hemv_tiles``): the
+    diagonal of a Hermitian matrix is real, so the imaginary part of the
+    stored diagonal is never read; it is dropped here.
+    """
     if lower:
-        low = torch.tril(tile)
-        return low + torch.tril(tile, -1).mH
-    up = torch.triu(tile)
-    return up + torch.triu(tile, 1).mH
+        full = torch.tril(tile) + torch.tril(tile, -1).mH
+    else:
+        full = torch.triu(tile) + torch.triu(tile, 1).mH
+    if full.is_complex():
+        full.diagonal().imag.zero_()
+    return full
 
 
 def _opc(dtype) -> Op:
@@ -48,7 +55,8 @@ def hermitian_multiplication(side: Side, uplo: UpLo, alpha, A: Matrix, B: Matrix
                              beta, C: Matrix, grid: Optional[CommGrid] = None) -> None:
     """C <- alpha A B + beta C (Left) or alpha B A + beta C (Right), A Hermitian.
 
-    Only the ``uplo`` triangle of A is referenced. Reference:
+    Only the ``uplo`` triangle of A is referenced, and of its diagonal only
+    the real part (as BLAS ``?hemm``). Reference:
     ``multiplication/hermitian/impl.h:69-213``.
     """
     da, db, dc = A.dist, B.dist, C.dist
